@@ -15,7 +15,20 @@ rank runs the identical SPMD sequence and the reductions are RCCL allreduces.
 
 value = algorithmic bytes of all ranks per step x steps / (max over ranks of the timed wall time).
 
-Beside the headline the JSON line carries (none of them inside the timed region):
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps (with
+the HIP-event ledger around every op: the roofline of the timed region itself), writes the last
+step's outputs if `--dump-outputs DIR` is given, and prints the JSON line; every figure below is
+then null.
+
+--dump-outputs DIR writes what the last timed step computed, as DIR/<name>.npy (float64):
+  s_rq, h_rq          the two gemm_inner results (m x k)
+  solution, residual  the m constructed solutions and the m residuals, at sample_blocks()'s fixed,
+                      seeded sample of global indices (whole vectors up to 2^18 elements)
+  errors              the m squared residual norms
+The inputs depend on the arguments alone (SEED, global-index seeded fills), so two builds run with
+the same arguments can be compared output for output.
+
+With --full the JSON line also carries (none of them inside the timed region):
   product_step  the same update as the product's solver runs it: construct_solution as ONE
                 write-only pass per space (ssp_gemm_outer_set, IterativeSolverTemplate.h:33-65 fused,
                 8N(k + m) B) and the residuals with their norms as one pass (construct_residual +
@@ -93,8 +106,8 @@ class Workload:
 
     def step(self):
         c = self.ctx
-        c.gemm_inner(self.rp, self.qp)
-        c.gemm_inner(self.rp, self.qa)
+        self.s_rq = c.gemm_inner(self.rp, self.qp)
+        self.h_rq = c.gemm_inner(self.rp, self.qa)
         for v in self.rp:
             c.fill(0.0, v)
         c.gemm_outer(self.coef, self.qp, self.rp)
@@ -103,10 +116,8 @@ class Workload:
         c.gemm_outer(self.coef, self.qa, self.ra)
         for i in range(self.m):
             c.axpy(-self.lam[i], self.rp[i], self.ra[i])
-        err = 0.0
-        for i in range(self.m):
-            err = max(err, c.dot(self.ra[i], self.ra[i]))
-        return err
+        self.errs = [c.dot(self.ra[i], self.ra[i]) for i in range(self.m)]
+        return max([0.0] + self.errs)
 
     def free(self):
         for v in self.rp + self.ra + self.qp + self.qa:
@@ -122,6 +133,66 @@ class Workload:
         c.gemm_outer_set(self.coef, self.qa, self.ra)
         nrm2 = c.axpy_pairs_norm(-self.lam, self.rp, self.ra)
         return float(np.max(nrm2))
+
+
+DUMP_BLOCK = 1024             # contiguous elements per sampled block
+DUMP_PER_VECTOR = 1 << 18     # elements of one vector in --dump-outputs (2 MB)
+DUMP_VECTOR_BYTES = 48 << 20  # all sampled vectors together: the whole dump stays under 64 MB
+
+
+def sample_blocks(n_global, nvec):
+    """--dump-outputs' sample of a vector of n_global elements, one of nvec: [(start, length)] in
+    global indices, ascending and disjoint.  The whole vector when it fits in the per-vector share;
+    else its first and its last DUMP_BLOCK elements and whole blocks between them drawn with SEED --
+    a function of (n_global, nvec) alone, so the same in every run and on every rank."""
+    per_vec = min(DUMP_PER_VECTOR, DUMP_VECTOR_BYTES // (8 * max(1, nvec)))
+    nb = max(2, per_vec // DUMP_BLOCK)
+    if n_global <= nb * DUMP_BLOCK:
+        return [(0, n_global)]
+    whole = n_global // DUMP_BLOCK  # >= nb; the last whole block may overlap the tail and is never drawn
+    pick = np.random.default_rng(SEED).choice(np.arange(1, whole - 1), size=nb - 2, replace=False)
+    starts = [0] + sorted(int(b) * DUMP_BLOCK for b in pick) + [n_global - DUMP_BLOCK]
+    return [(s, DUMP_BLOCK) for s in starts]
+
+
+def download_sample(ctx, vecs, blocks, lo, hi):
+    """The elements of `blocks` that lie in this rank's index range [lo, hi) of each vector, as rows
+    of len(vecs) x (sample length); zero where another rank holds the element."""
+    out = np.zeros((len(vecs), sum(ln for _, ln in blocks)))
+    for j, v in enumerate(vecs):
+        pos = 0
+        for s, ln in blocks:
+            a, b = max(s, lo), min(s + ln, hi)
+            if a < b:
+                dst = out[j, pos + a - s:pos + b - s]
+                code = ctx.lib.ssp_download(ctx.handle, dst.ctypes.data, v.ptr + 8 * (a - lo), b - a)
+                if code:
+                    raise sh.SspError(code, ctx.lib.ssp_last_error().decode())
+            pos += ln
+    return out
+
+
+def dump_outputs(dirname, ctx, wl, borders, rank, world):
+    """--dump-outputs: the results of the step that ran last (see the module docstring).  Collective
+    at N > 1: every rank sends its part of the sample, rank 0 writes the files."""
+    n_global = borders[-1]
+    blocks = sample_blocks(n_global, 2 * wl.m)
+    index = np.concatenate([np.arange(s, s + ln) for s, ln in blocks])
+    owner = np.searchsorted(np.asarray(borders[1:]), index, side="right")
+    arrays = {"s_rq": wl.s_rq, "h_rq": wl.h_rq, "errors": np.asarray(wl.errs, dtype=np.float64)}
+    for name, vecs in (("solution", wl.rp), ("residual", wl.ra)):
+        part = download_sample(ctx, vecs, blocks, borders[rank], borders[rank + 1])
+        if world > 1:
+            parts = [np.frombuffer(b, dtype=np.float64).reshape(part.shape) for b in ctx.allgather_bytes(part.tobytes())]
+            part = np.empty_like(part)
+            for r, p in enumerate(parts):
+                part[:, owner == r] = p[:, owner == r]
+        arrays[name] = part
+    if rank == 0:
+        os.makedirs(dirname, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def op_kernels(op, m):
@@ -541,6 +612,12 @@ def main():
     ap.add_argument("--n-global", type=float, default=1e8, help="global vector length")
     ap.add_argument("--roots", type=int, default=8)
     ap.add_argument("--qsize", type=int, default=48)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: the product's step, "
+                         "the CPU baselines and the sustained phase, the step at N / 10, the whole solves")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results to DIR/<name>.npy (float64; large vectors as a "
+                         "fixed seeded sample)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-n", type=float, default=CPU_N, help="vector length of the 1-core CPU baseline step")
@@ -561,6 +638,8 @@ def main():
     ap.add_argument("--mfma-json", default=os.path.join(ROOT, "profiles", "r3", "mfma_util_n1e8.json"),
                     help="rocprofv3 --pmc MfmaUtil summary of this workload (mfma.mfma_util_pct)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs writes the last timed step's results: --steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -616,6 +695,9 @@ def main():
     elapsed = t1 - t0
     if world > 1:  # max over ranks
         elapsed = max(struct.unpack("<d", b)[0] for b in ctx.allgather_bytes(struct.pack("<d", elapsed)))
+    dumped = None
+    if args.dump_outputs:  # before anything else touches the vectors
+        dumped = dump_outputs(args.dump_outputs, ctx, wl, borders, rank, world)
     ledger_steps = args.steps
     if not timed_ledger:
         # Per-kernel HIP-event ledger over a few extra steps (not part of the timed region).
@@ -627,32 +709,35 @@ def main():
         ledger_steps = args.ledger_steps
     led = ctx.ledger()
 
-    # The product's own form of the same update (not the headline; see the module docstring).
-    for _ in range(2):
+    # Everything from here to the JSON line is --full's: a plain run has its headline and goes there.
+    product = None
+    if args.full:
+        # The product's own form of the same update (not the headline; see the module docstring).
+        for _ in range(2):
+            wl.product_step()
+        ctx.synchronize()
+        barrier()
+        tp = time.perf_counter()
+        p_steps = max(5, args.steps // 4)
+        for _ in range(p_steps):
+            wl.product_step()
+        ctx.synchronize()
+        tp = time.perf_counter() - tp
+        if world > 1:
+            tp = max(struct.unpack("<d", b)[0] for b in ctx.allgather_bytes(struct.pack("<d", tp)))
+        ctx.ledger_reset()
+        ctx.ledger_enable(True)
         wl.product_step()
-    ctx.synchronize()
-    barrier()
-    tp = time.perf_counter()
-    p_steps = max(5, args.steps // 4)
-    for _ in range(p_steps):
-        wl.product_step()
-    ctx.synchronize()
-    tp = time.perf_counter() - tp
-    if world > 1:
-        tp = max(struct.unpack("<d", b)[0] for b in ctx.allgather_bytes(struct.pack("<d", tp)))
-    ctx.ledger_reset()
-    ctx.ledger_enable(True)
-    wl.product_step()
-    ctx.ledger_enable(False)
-    pled = ctx.ledger()
-    product = {
-        "ms_per_step": round(1e3 * tp / p_steps, 4),
-        "bytes_per_step": product_step_bytes(n_global, m, k),
-        "GBs": round(product_step_bytes(n_global, m, k) * p_steps / tp / 1e9, 2),
-        "vs_headline_step_time": None,
-        "ops": {op: {"calls_per_step": v["calls"], "avg_us": round(1e3 * v["ms"] / v["calls"], 2),
-                     "GBs": round(v["bytes"] / (v["ms"] / 1e3) / 1e9, 1)} for op, v in pled.items()},
-    }
+        ctx.ledger_enable(False)
+        pled = ctx.ledger()
+        product = {
+            "ms_per_step": round(1e3 * tp / p_steps, 4),
+            "bytes_per_step": product_step_bytes(n_global, m, k),
+            "GBs": round(product_step_bytes(n_global, m, k) * p_steps / tp / 1e9, 2),
+            "vs_headline_step_time": None,
+            "ops": {op: {"calls_per_step": v["calls"], "avg_us": round(1e3 * v["ms"] / v["calls"], 2),
+                         "GBs": round(v["bytes"] / (v["ms"] / 1e3) / 1e9, 1)} for op, v in pled.items()},
+        }
     # CPU baselines (rank 0 of a 1-GPU run) on ONE pinned host core, in a thread beside the GPU work
     # that follows (the reference loops release the GIL inside their C calls): the headline step's op
     # sequence at N = 1e7, DRAM-resident, then the C2 Davidson solve (BASELINE.md §3's "In-solver"
@@ -660,7 +745,7 @@ def main():
     # long-run rate beside the timed region -- and the GPU solves run; host-parallel (all host threads)
     # and the DRAM-resident single calls come last, GPU idle.
     sustained, cb, th, box = None, None, None, {}
-    run_cpu = world == 1 and not args.no_cpu_baseline
+    run_cpu = args.full and world == 1 and not args.no_cpu_baseline
     if run_cpu:
         log("CPU baselines (oracle, 1 pinned core) in a thread beside the GPU work...")
 
@@ -688,7 +773,7 @@ def main():
     # The same headline step at a tenth of the length (BASELINE config C2's N = 1e7 sharded alike):
     # the rate where launch and reduction latencies weigh ten times more.
     small = None
-    if not args.no_small and n_global >= 10:
+    if args.full and not args.no_small and n_global >= 10:
         ns_global = n_global // 10
         sb = distribution(ns_global, world)
         wls = Workload(ctx, sb[rank + 1] - sb[rank], sb[rank], m, k)
@@ -726,7 +811,7 @@ def main():
                               "bytes_per_launch": es["bytes"] / es["calls"],
                               "ledger": "HIP events over 5 steps after the timed region"}}
     solve = solve_diis = gpu_c2 = shard = None
-    if not args.no_in_solver:
+    if args.full and not args.no_in_solver:
         solve = in_solver(ctx, n_global, world, barrier)
         solve_diis = in_solver(ctx, n_global, world, barrier, kind="diis")
         if world == 1 and n_global >= 8:
@@ -761,6 +846,8 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / args.steps, 4),
             "higher_is_better": True,
+            "full": args.full,
+            "outputs": dumped,
             "scaling": "strong",
             "vs_baseline": None,
             "dtype": "f64",
@@ -804,7 +891,8 @@ def main():
                         "first_solve_wall_s": solve["wall_s_cold"] if solve else None,
                         "warm_solve_wall_s": solve["wall_s"] if solve else None},
         }
-        product["vs_headline_step_time"] = round(product["ms_per_step"] / (1e3 * elapsed / args.steps), 4)
+        if product is not None:
+            product["vs_headline_step_time"] = round(product["ms_per_step"] / (1e3 * elapsed / args.steps), 4)
         if "gemm_inner" in led and world == 1:
             # gemm_inner runs on the f64 matrix cores: live MFMA rate from the ledger (2 m k N flops
             # per call) against the dense f64 MFMA peak, and the PMC-measured MfmaUtil beside it.

@@ -4,13 +4,16 @@ CPU: shard borders, algorithmic bytes per step, the PMC-summary lookup, the CPU 
 GPU: a short N = 1 run, and N = 2 launched exactly as the driver launches it
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 ...`)
 with `--comm host`, two ranks on the box's one device (RCCL refuses duplicate GPUs; the RCCL calls
-themselves are covered by test_rccl_gpu.py).
+themselves are covered by test_rccl_gpu.py).  These runs pass `--full`: they assert figures beside the
+headline.  The plain run (the headline alone) and `--dump-outputs` have tests of their own at the end:
+over the host emulation with one and two ranks, and on the GPU.
 """
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import oracle
@@ -106,7 +109,7 @@ def parse(out):
 @pytest.mark.gpu
 def test_bench_single_gpu():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--n-global", "4e6",
-           "--cpu-seconds", "0.5", "--cpu-n", "1e6", "--cpu-solve-n", "1e5"]
+           "--cpu-seconds", "0.5", "--cpu-n", "1e6", "--cpu-solve-n", "1e5", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-4000:]
     d = parse(r.stdout)
@@ -128,7 +131,7 @@ def test_bench_two_ranks_host_hub():
         env.pop(v, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--n-global", "4000001", "--comm", "host"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--n-global", "4000001", "--comm", "host", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = parse(r.stdout)
@@ -146,7 +149,7 @@ def test_bench_two_ranks_rccl_refused_falls_back_to_the_host_hub():
         env.pop(v, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--n-global", "4000001", "--no-in-solver"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--n-global", "4000001", "--no-in-solver", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = parse(r.stdout)
@@ -164,7 +167,7 @@ def test_bench_two_ranks_peer_memory(comm):
         env.pop(v, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--n-global", "4000001", "--comm", comm]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--n-global", "4000001", "--comm", comm, "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = parse(r.stdout)
@@ -184,7 +187,7 @@ def test_bench_eight_ranks_emulated():
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(ROOT, "tests", "bench_emul.py"), "bench",
            "--gpus", "8", "--steps", "2", "--warmup", "1", "--ledger-steps", "1", "--n-global", str(n),
-           "--comm", "host"]
+           "--comm", "host", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = parse(r.stdout)
@@ -231,10 +234,110 @@ def test_bench_eight_ranks_rccl_join_failure_falls_back_to_the_host_hub():
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(ROOT, "tests", "bench_emul.py"), "bench",
            "--gpus", "8", "--steps", "2", "--warmup", "1", "--ledger-steps", "1", "--n-global", str(n),
-           "--no-in-solver"]
+           "--no-in-solver", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = parse(r.stdout)
     assert d["n_gpus"] == 8 and d["comm"] == "host" and "host-hub" in d["config"]["parallelism"]
     assert d["comm_fallback"]["from"] == "rccl" and d["comm_fallback"]["failed_ranks"] == [3]
     assert r.stderr.count("every rank falls back to the host hub") == 8
+
+
+# -- the plain run (no --full) and --dump-outputs ---------------------------------------------------
+
+FULL_ONLY = ("product_step", "headline_step_at_n_div_10", "in_solver", "in_solver_diis", "in_solver_c4_shard",
+             "cpu_baseline", "sustained")
+DUMP_N = 300_007  # beyond the 2^18 elements --dump-outputs keeps of one vector, odd, no multiple of a block
+_dump_ref = {}
+
+
+def dump_reference():
+    """What one steady-state step leaves at DUMP_N (m = 8, k = 48), in numpy from the oracle's copy of
+    the input generator, with the worst-case rounding bound of each array (any summation order):
+    {name: (value, bound)}, the vectors at every index.  Computed once."""
+    if not _dump_ref:
+        m, k, n, eps = 8, 48, DUMP_N, 2.0**-53
+        rng = np.random.default_rng(bench.SEED)
+        coef, lam = rng.uniform(-0.1, 0.1, (k, m)), rng.uniform(0.5, 2.0, m)
+        qp = np.stack([oracle.random_vector(n, bench.SEED, 2 * m + i) for i in range(k)])
+        qa = np.stack([oracle.random_vector(n, bench.SEED, 2 * m + k + i) for i in range(k)])
+        sol, asol = coef.T @ qp, np.abs(coef).T @ np.abs(qp)
+        act, aact = coef.T @ qa, np.abs(coef).T @ np.abs(qa)
+        res, ares = act - lam[:, None] * sol, aact + lam[:, None] * asol
+        # a sum of t products: |error| <= (t + 1) eps sum |terms|; an operand with error e adds e |other|
+        bsol, bres = (k + 1) * eps * asol, (k + 3) * eps * ares
+        _dump_ref.update(
+            solution=(sol, bsol), residual=(res, bres),
+            s_rq=(sol @ qp.T, (n + 1) * eps * (np.abs(sol) @ np.abs(qp).T) + bsol @ np.abs(qp).T),
+            h_rq=(sol @ qa.T, (n + 1) * eps * (np.abs(sol) @ np.abs(qa).T) + bsol @ np.abs(qa).T),
+            errors=((res * res).sum(1), (n + 1) * eps * (res * res).sum(1) + 2 * (bres * np.abs(res)).sum(1)))
+    return _dump_ref
+
+
+def check_dump(d, out, world=1):
+    """The plain run's line `d` and the files it wrote to `out` against dump_reference()."""
+    assert d["full"] is False and all(d[key] is None for key in FULL_ONLY)
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["n_gpus"] == world
+    assert d["ops"]["gemm_outer"]["calls_per_step"] == 2  # the ledger of the timed steps themselves
+    blocks = bench.sample_blocks(DUMP_N, 16)
+    index = np.concatenate([np.arange(s, s + ln) for s, ln in blocks])
+    ref = dump_reference()
+    assert sorted(os.listdir(out)) == sorted(name + ".npy" for name in ref)
+    total = 0
+    for name, (want, bound) in ref.items():
+        got = np.load(os.path.join(out, name + ".npy"))
+        total += got.nbytes
+        assert got.dtype == np.float64 and d["outputs"][name] == list(got.shape)
+        if name in ("solution", "residual"):
+            want, bound = want[:, index], bound[:, index]
+        assert got.shape == want.shape
+        # the numpy reference rounds too: twice the bound
+        assert np.all(np.abs(got - want) <= 2 * bound), (name, np.max(np.abs(got - want) / bound))
+    assert total <= 64 << 20
+
+
+def test_sample_blocks():
+    for n, nvec in [(10**8, 16), (DUMP_N, 16), (10**8 + 3, 64), (2**31 + 5, 2)]:
+        blocks = bench.sample_blocks(n, nvec)
+        assert blocks == bench.sample_blocks(n, nvec)  # seeded: the same in every run
+        assert blocks[0][0] == 0 and sum(blocks[-1]) == n  # both ends of the vector
+        assert all(a + la <= b for (a, la), (b, _) in zip(blocks, blocks[1:]))  # ascending, disjoint
+        assert 8 * nvec * sum(ln for _, ln in blocks) <= 48 << 20
+    assert sum(ln for _, ln in bench.sample_blocks(10**8, 16)) == 2**18
+    assert bench.sample_blocks(2**18, 16) == [(0, 2**18)] and bench.sample_blocks(7, 16) == [(0, 7)]
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_bench_plain_run_dumps_outputs_emulated(tmp_path, world):
+    """The plain run over the host emulation: only the headline (everything --full measures is null),
+    and --dump-outputs' files hold the last step's results -- at world 2 gathered from both shards."""
+    env = dict(os.environ)
+    for v in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(v, None)
+    launch = [] if world == 1 else ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
+                                    "--master-addr", "127.0.0.1", "--master-port", str(free_port())]
+    out = str(tmp_path / "out")
+    cmd = [sys.executable] + launch + [os.path.join(ROOT, "tests", "bench_emul.py"), "bench", "--gpus", str(world),
+                                       "--steps", "2", "--warmup", "1", "--n-global", str(DUMP_N), "--comm", "host",
+                                       "--dump-outputs", out]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    check_dump(parse(r.stdout), out, world)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """The plain run on the GPU, twice with the same arguments: the same files bit for bit, and they
+    hold the last step's results."""
+    outs = []
+    for name in ("a", "b"):
+        outs.append(str(tmp_path / name))
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+               "--n-global", str(DUMP_N), "--dump-outputs", outs[-1]]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-4000:]
+        d = parse(r.stdout)
+    check_dump(d, outs[1])
+    for f in os.listdir(outs[0]):
+        with open(os.path.join(outs[0], f), "rb") as fa, open(os.path.join(outs[1], f), "rb") as fb:
+            assert fa.read() == fb.read(), f

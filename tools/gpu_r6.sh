@@ -25,7 +25,7 @@ step() {
 for s in ${1//,/ }; do
   case $s in
     bench)
-      step bench 600 python -u bench.py || exit $?
+      step bench 600 python -u bench.py --full || exit $?
       grep '^{' "$OUT/bench.log" > "$OUT/bench.json" || true
       ;;
     c4ledger)
@@ -103,14 +103,14 @@ for s in ${1//,/ }; do
     benchprof)
       rm -rf "$OUT/benchprof"
       step benchprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/benchprof" -o run --output-format csv -- \
-        python3 -u bench.py --steps 10 --warmup 3 || exit $?
+        python3 -u bench.py --full --steps 10 --warmup 3 || exit $?
       grep '^{' "$OUT/benchprof.log" > "$OUT/bench_under_rocprof.json" || true
       ;;
     pmcbench)
       for c in FETCH_SIZE WRITE_SIZE; do
         rm -rf "$OUT/pmcb_$c"
         step "pmcb_$c" 600 rocprofv3 --pmc "$c" --kernel-trace -d "$OUT/pmcb_$c" -o run --output-format csv -- \
-          python3 bench.py --steps 2 --warmup 1 --ledger-steps 1 --no-cpu-baseline --no-in-solver --no-small || exit $?
+          python3 bench.py --full --steps 2 --warmup 1 --ledger-steps 1 --no-cpu-baseline --no-in-solver --no-small || exit $?
       done
       ;;
     pmcc4)

@@ -4,7 +4,7 @@
 #   tools/gpu_session.sh STEPS [args...]      STEPS: comma-separated, run in order, e.g. tests,smoke,bench
 #     tests   [pytest args]   python -m pytest tests -m gpu -v (every test named as it starts and ends)
 #     smoke                    __graft_entry__.smoke()
-#     bench   [bench args]     python bench.py
+#     bench   [bench args]     python bench.py --full (every figure beside the headline)
 #     prof    [bench args]     rocprofv3 --kernel-trace --stats of a short bench run
 #     pmc     [bench args]     HBM traffic counters (FETCH_SIZE, WRITE_SIZE), one --pmc pass each
 #     mfma    [bench args]     matrix-core counters of the bench step and of the per-shape bench
@@ -48,13 +48,13 @@ for s in ${steps//,/ }; do
       step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" || exit $?
       ;;
     bench)
-      step bench 900 python -u bench.py "$@" || exit $?
+      step bench 900 python -u bench.py --full "$@" || exit $?
       grep '^{' "$OUT/bench.log" >"$OUT/bench.json" || true
       ;;
     prof)
       rm -rf "$OUT/prof"
       step rocprof 900 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-        python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline "$@" || exit $?
+        python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline "$@" || exit $?
       # the bench line of the profiled process itself: its ledger and the kernel statistics come
       # from the same allocation
       grep '^{' "$OUT/rocprof.log" >"$OUT/bench_rocprof.json" || true
@@ -63,14 +63,14 @@ for s in ${steps//,/ }; do
       for c in FETCH_SIZE WRITE_SIZE; do
         rm -rf "$OUT/pmc_$c"
         step "pmc_$c" 600 rocprofv3 --pmc "$c" --kernel-trace -d "$OUT/pmc_$c" -o run --output-format csv -- \
-          python3 bench.py --steps 2 --warmup 1 --ledger-steps 1 --no-cpu-baseline --no-in-solver --no-small \
+          python3 bench.py --full --steps 2 --warmup 1 --ledger-steps 1 --no-cpu-baseline --no-in-solver --no-small \
           "$@" || exit $?
       done
       ;;
     mfma)
       rm -rf "$OUT/pmc_mfma" "$OUT/pmc_mfma_shapes"
       step pmc_mfma 600 rocprofv3 --pmc MfmaUtil MfmaFlopsF64 SQ_INSTS_VALU_MFMA_F64 --kernel-trace \
-        -d "$OUT/pmc_mfma" -o run --output-format csv -- python3 bench.py --steps 2 --warmup 1 --ledger-steps 1 \
+        -d "$OUT/pmc_mfma" -o run --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --ledger-steps 1 \
         --no-cpu-baseline --no-in-solver --no-small "$@" || exit $?
       step pmc_mfma_shapes 600 rocprofv3 --pmc MfmaUtil MfmaFlopsF64 SQ_INSTS_VALU_MFMA_F64 --kernel-trace \
         -d "$OUT/pmc_mfma_shapes" -o run --output-format csv -- python3 tools/shapes_bench.py --reps 1 \
