@@ -52,8 +52,12 @@ const char* ssp_version(void);
 int ssp_device_count(void);
 int ssp_ctx_create(int device, ssp_ctx** out);
 int ssp_ctx_destroy(ssp_ctx* ctx);
-/* The hipStream_t all ops of this context run on (for event timing by callers). */
+/* The hipStream_t all ops of this context run on (for event timing by callers, and for their own
+ * kernels on the library's vectors).  Stores every deferred zero fill (ssp_fill) first: call it, or
+ * ssp_synchronize, AFTER the library calls whose results foreign code is going to read -- a stream
+ * handle taken earlier does not order foreign work behind a fill that was deferred later. */
 void* ssp_ctx_stream(ssp_ctx* ctx);
+/* Stores every deferred zero fill, then waits until the stream is idle. */
 int ssp_synchronize(ssp_ctx* ctx);
 /* Caching device allocator (HBM arena): Q vectors are created and destroyed every iteration
  * (reference itsolv/subspace/QSpace.h:80-84), so freed blocks are recycled by size. */
@@ -129,7 +133,29 @@ int ssp_ledger_entry(ssp_ctx* ctx, int i, const char** name, long long* calls, d
 
 /* ---- dense (R x R, Q x Q, R x Q) operations: reference ArrayHandlerIterable.h:46-90,
  *      DistrArray.cpp:43-138 ------------------------------------------------------------- */
-/* x[:] = alpha                         reference ArrayHandlerIterable.h:59-63 */
+/* x[:] = alpha                         reference ArrayHandlerIterable.h:59-63
+ * A fill with +0.0 of a vector longer than exact_max is deferred: the call launches nothing and the
+ * library remembers the range (up to 64 of them).  Every later entry point of the context first stores
+ * the remembered zeros (one fill kernel each, in the order of the calls), so every library call, copy
+ * and reduction sees exactly the memory an immediate fill would have left, with these exceptions that
+ * do less work for the same bits:
+ *   ssp_gemm_outer[_scaled]  whose destinations are all exactly deferred vectors (same address and
+ *                            length, none twice, no destination scale): runs as ssp_gemm_outer_set, the
+ *                            zeros are never written or read (fill(0) + gemm_outer in one write-only
+ *                            pass, the reference's construct_solution); otherwise the fills of its
+ *                            operands are stored first and it runs read-modify-write;
+ *   ssp_gemm_outer_set[_scaled], ssp_copy, ssp_scal_copy, another ssp_fill
+ *                            that overwrite a deferred vector whole: its zeros are never written;
+ *   ssp_free                 of the block that holds it: likewise.
+ * Deferred fills that a call does not touch stay deferred across these.  Code that reads device
+ * memory WITHOUT a library call (its own kernels, hipMemcpy) must take ssp_ctx_stream or call
+ * ssp_synchronize after the fill.  -0.0, non-zero values and short vectors are filled at once.
+ * Lifetime: the zeros may be written at any later entry point of the context, so memory the library
+ * did not allocate (a vector over the caller's own hipMalloc block, from C, Fortran or a non-owning
+ * view) must stay allocated until a call that stores or drops the fill -- any call other than the
+ * exceptions above, ssp_ctx_stream or ssp_synchronize -- has returned; blocks of ssp_alloc are safe,
+ * ssp_free drops their fills.
+ * SSP_DEFER_FILL=0 in the environment at ssp_ctx_create: every fill is launched at once. */
 int ssp_fill(ssp_ctx* ctx, double alpha, double* x, size_t n);
 /* x[:] *= alpha                        reference ArrayHandlerIterable.h:54-57 */
 int ssp_scal(ssp_ctx* ctx, double alpha, double* x, size_t n);

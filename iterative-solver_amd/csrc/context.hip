@@ -50,6 +50,11 @@ int use_device(ssp_ctx* ctx) {
   return SSP_OK;
 }
 
+int enter(ssp_ctx* ctx) {
+  SSP_TRY(use_device(ctx));
+  return flush_fills(ctx);
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 unsigned stream_grid(const ssp_ctx* ctx, size_t work_items, unsigned per_thread, unsigned blocks_per_cu) {
@@ -422,7 +427,7 @@ int ssp_ledger_reserve(ssp_ctx* ctx, int n) {
 
 int ssp_ledger_count(ssp_ctx* ctx) {
   if (!ctx) return -1;
-  if (ssp::use_device(ctx) != SSP_OK || ssp::ledger_resolve(ctx) != SSP_OK) return -1;
+  if (ssp::enter(ctx) != SSP_OK || ssp::ledger_resolve(ctx) != SSP_OK) return -1;
   return int(ctx->ledger.size());
 }
 
@@ -476,6 +481,7 @@ int ssp_ctx_create(int device, ssp_ctx** out) {
     ctx->synth_window = std::string(ss) == "window";
   }
   if (const char* sm = std::getenv("SSP_SYNTH_MERGE")) ctx->synth_merge = std::atoi(sm) != 0;
+  if (const char* df = std::getenv("SSP_DEFER_FILL")) ctx->defer_fill = std::atoi(df) != 0;
   if (const char* ct = std::getenv("SSP_COMM_TIMEOUT_S")) {
     const double v = std::atof(ct);
     if (v > 0) ctx->comm_timeout_s = v;
@@ -503,6 +509,7 @@ int ssp_ctx_create(int device, ssp_ctx** out) {
 int ssp_ctx_destroy(ssp_ctx* ctx) {
   if (!ctx) return SSP_OK;
   (void)hipSetDevice(ctx->device);
+  ctx->pending_fills.clear();  // nobody can read the vectors of a destroyed context
   (void)ssp::p2p_detach(ctx);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->comm) ncclCommDestroy(ctx->comm);
@@ -535,7 +542,13 @@ int ssp_ctx_destroy(ssp_ctx* ctx) {
   return SSP_OK;
 }
 
-void* ssp_ctx_stream(ssp_ctx* ctx) { return ctx ? reinterpret_cast<void*>(ctx->stream) : nullptr; }
+// The hand-off of the stream to foreign code: work the caller queues on it may read any vector, so
+// every pending zero fill is stored first (ssp_last_error keeps a failure to launch one).
+void* ssp_ctx_stream(ssp_ctx* ctx) {
+  if (!ctx) return nullptr;
+  (void)ssp::enter(ctx);
+  return reinterpret_cast<void*>(ctx->stream);
+}
 
 int ssp_synchronize(ssp_ctx* ctx) {
   SSP_CHECK_CTX(ctx);
@@ -575,9 +588,12 @@ int ssp_alloc(ssp_ctx* ctx, size_t n, double** out) {
 
 int ssp_free(ssp_ctx* ctx, double* p) {
   if (!p) return SSP_OK;
-  SSP_CHECK_CTX(ctx);
+  SSP_CHECK_CTX_KEEP_FILLS(ctx);
   auto it = ctx->live_blocks.find(p);
   if (it == ctx->live_blocks.end()) return ssp::set_error(SSP_ERR_ARG, "ssp_free: pointer not from ssp_alloc");
+  // Pending zero fills inside the block are dropped before it returns to the arena: a later flush must
+  // never write into a freed or recycled block.
+  SSP_TRY(ssp::overwrite_fills(ctx, p, it->second / sizeof(double)));
   // Stream-ordered reuse: a later ssp_alloc on the same stream can only be used by work queued
   // after every op that touched this block, so no synchronisation is needed here.
   ctx->free_blocks.emplace(it->second, p);

@@ -1486,9 +1486,13 @@ int ssp_gemm_inner_scaled(ssp_ctx* ctx, const double* const* xx, const double* x
 namespace {
 int gemm_outer_impl(ssp_ctx* ctx, const double* alphas, const double* const* xx, const double* xs, int k,
                     double* const* yy, const double* ys, int m, size_t n, bool set) {
-  SSP_CHECK_CTX(ctx);
+  SSP_CHECK_CTX_KEEP_FILLS(ctx);
   if (m < 0 || k < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_gemm_outer: negative dimension");
   if (set && k == 0) {
+    // These zero fills may stay deferred past the return, like a caller's own ssp_fill(0): the next
+    // library call stores them.  A caller that hands yy on to code of its own (the host layer's
+    // data_wo() destinations reaching a user's action) relies on the rule of include/subspace_hip.h:
+    // take ssp_ctx_stream or ssp_synchronize before foreign code touches the memory.
     for (int j = 0; j < m; ++j) SSP_TRY(ssp_fill(ctx, 0.0, yy[j], n));
     return SSP_OK;
   }
@@ -1504,9 +1508,35 @@ int gemm_outer_impl(ssp_ctx* ctx, const double* alphas, const double* const* xx,
   for (int j = 0; j < m; ++j)
     for (int i = 0; i < k; ++i)
       if (yy[j] == xx[i]) return ssp::set_error(SSP_ERR_ARG, "ssp_gemm_outer: a destination aliases a source");
+  // Pending zero fills (pending_fill.h).  The sources are read: theirs are stored.  The write-only
+  // form overwrites its destinations: the entries inside them are dropped.  The read-modify-write form
+  // consumes: when every destination is exactly a pending entry (so they are distinct and disjoint),
+  // carries no deferred scale and is outside exact mode, the entries are dropped and the first source
+  // chunk of every destination group runs as the SET instantiation, whose accumulators start from the
+  // +0.0 that the read-modify-write form would have loaded -- the same bits without writing the zeros
+  // and reading them back.  All or nothing: otherwise every entry a destination touches is stored and
+  // the call runs as it always did.  Entries no operand touches stay pending.
+  bool consume = false;
+  if (!ctx->pending_fills.empty()) {
+    for (int i = 0; i < k; ++i) SSP_TRY(ssp::flush_fills_over(ctx, xx[i], n));
+    if (set) {
+      for (int j = 0; j < m; ++j) SSP_TRY(ssp::overwrite_fills(ctx, yy[j], n));
+    } else {
+      consume = !any_scaled(ys, m) && !ssp::exact_mode(ctx, n);
+      for (int j = 0; consume && j < m; ++j) {
+        consume = ctx->pending_fills.find_exact(yy[j], n) >= 0;
+        for (int i = 0; consume && i < j; ++i) consume = yy[i] != yy[j];
+      }
+      for (int j = 0; j < m; ++j) {
+        if (consume) ctx->pending_fills.erase(ctx->pending_fills.find_exact(yy[j], n));
+        else SSP_TRY(ssp::flush_fills_over(ctx, yy[j], n));
+      }
+    }
+  }
+  const bool set0 = set || consume;  // the destinations are not read by their first launch
   // Destinations are independent; sources are applied in increasing order, in groups that fit
   // the kernel argument block, so each destination sees the reference's summation order.
-  ssp::LedgerScope ls(ctx, set ? "gemm_outer_set" : "gemm_outer", 8.0 * n * (k + (set ? 1.0 : 2.0) * m));
+  ssp::LedgerScope ls(ctx, set ? "gemm_outer_set" : "gemm_outer", 8.0 * n * (k + (set0 ? 1.0 : 2.0) * m));
   if (ssp::exact_mode(ctx, n)) return ssp::exact_outer(ctx, alphas, xx, xs, k, yy, ys, m, n, set);
   for (int j0 = 0; j0 < m; j0 += ssp::kOuterDst) {
     const int mm = std::min(ssp::kOuterDst, m - j0);
@@ -1517,14 +1547,14 @@ int gemm_outer_impl(ssp_ctx* ctx, const double* alphas, const double* const* xx,
       OuterArgs a{};
       a.m = mm;
       a.k = std::min(ssp::kOuterSrc, k - i0);
-      a.set = (set && i0 == 0) ? 1 : 0;
+      a.set = (set0 && i0 == 0) ? 1 : 0;
       a.n = n;
       for (int i = 0; i < a.k; ++i) a.x[i] = xx[i0 + i];
       for (int j = 0; j < mm; ++j) a.y[j] = yy[j0 + j];
       // deferred scales: every source's; the destinations' on their first read only (i0 == 0)
       std::vector<double> scl(size_t(a.k + mm), 1.0);
       for (int i = 0; i < a.k; ++i) scl[size_t(i)] = xs ? xs[i0 + i] : 1.0;
-      for (int j = 0; j < mm; ++j) scl[size_t(a.k + j)] = (ys && i0 == 0 && !set) ? ys[j0 + j] : 1.0;
+      for (int j = 0; j < mm; ++j) scl[size_t(a.k + j)] = (ys && i0 == 0 && !set0) ? ys[j0 + j] : 1.0;
       if (any_scaled(scl.data(), int(scl.size()))) {
         void* ps;
         SSP_TRY(ssp::upload_small(ctx, scl.data(), scl.size() * sizeof(double), &ps));

@@ -357,7 +357,8 @@ int ssp_sparse_copy(ssp_ctx* ctx, double* x, size_t n, size_t offset, const size
                     size_t nnz) {
   SSP_CHECK_CTX(ctx);
   SSP_TRY(check_entries(idx, val, nnz, "ssp_sparse_copy"));
-  SSP_TRY(ssp_fill(ctx, 0.0, x, n));
+  // launched at once, not deferred: the scatter below writes into x in this same call
+  SSP_TRY(ssp::fill_now(ctx, 0.0, x, n));
   std::vector<unsigned long long> li;
   std::vector<double> lv;
   filter_local(idx, val, nnz, n, offset, li, lv);
@@ -671,6 +672,9 @@ int solution_impl(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const 
   else
     SSP_TRY(ssp_gemm_outer_set_scaled(ctx, alphas, xx, xs, k, yy, m, n));
   if (uidx.empty()) return SSP_OK;
+  // with no dense source the write-only pass above is m deferred zero fills: the fix-up below writes
+  // into those vectors, so they are stored first
+  SSP_TRY(ssp::flush_fills(ctx));
   ConstructFixArgs a{};
   unsigned long long *dptr, *dli;
   double* dv;

@@ -13,6 +13,7 @@
 // CU count), then a fixed-order fold (by the last workgroup to finish for small results,
 // ssp::fold_tail; else the k_reduce_partials pass).
 #include <algorithm>
+#include <cmath>
 
 #include "ssp_internal.h"
 
@@ -351,18 +352,65 @@ int launch_reduce_partials(ssp_ctx* ctx, const double* partial, int nblocks, int
   SSP_TRY_HIP(hipGetLastError());
   return SSP_OK;
 }
+int fill_now(ssp_ctx* ctx, double alpha, double* x, size_t n) {
+  SSP_TRY(check_vec(x, n, "ssp_fill"));
+  if (n == 0) return SSP_OK;
+  LedgerScope ls(ctx, "fill", 8.0 * n);
+  SSP_LAUNCH(k_fill, dim3(stream_grid(ctx, n / 2 + 1, 1, 64)), dim3(kBlock), 0, ctx->stream, x, n, alpha);
+  SSP_TRY_HIP(hipGetLastError());
+  return SSP_OK;
+}
+
+namespace {
+// The table's `flush` callable: one k_fill(+0.0) per entry, exactly the launch the eager ssp_fill
+// makes; the first failure is kept and the remaining entries are still taken out of the table.
+struct FillFlusher {
+  ssp_ctx* ctx;
+  int status = SSP_OK;
+  void operator()(double* p, size_t n) {
+    const int s = fill_now(ctx, 0.0, p, n);
+    if (status == SSP_OK) status = s;
+  }
+};
+}  // namespace
+
+int flush_fills(ssp_ctx* ctx) {
+  if (ctx->pending_fills.empty()) return SSP_OK;
+  FillFlusher f{ctx};
+  ctx->pending_fills.drain(f);
+  return f.status;
+}
+
+int flush_fills_over(ssp_ctx* ctx, const void* p, size_t n) {
+  if (ctx->pending_fills.empty()) return SSP_OK;
+  FillFlusher f{ctx};
+  ctx->pending_fills.flush_overlap(p, n, f);
+  return f.status;
+}
+
+int overwrite_fills(ssp_ctx* ctx, const void* p, size_t n) {
+  if (ctx->pending_fills.empty()) return SSP_OK;
+  FillFlusher f{ctx};
+  ctx->pending_fills.overwrite(p, n, f);
+  return f.status;
+}
 }  // namespace ssp
 
 extern "C" {
 
 int ssp_fill(ssp_ctx* ctx, double alpha, double* x, size_t n) {
-  SSP_CHECK_CTX(ctx);
-  SSP_TRY(check_vec(x, n, "ssp_fill"));
-  if (n == 0) return SSP_OK;
-  ssp::LedgerScope ls(ctx, "fill", 8.0 * n);
-  SSP_LAUNCH(k_fill, dim3(ssp::stream_grid(ctx, n / 2 + 1, 1, 64)), dim3(kBlock), 0, ctx->stream, x, n, alpha);
-  SSP_TRY_HIP(hipGetLastError());
-  return SSP_OK;
+  SSP_CHECK_CTX_KEEP_FILLS(ctx);
+  // A fill with +0.0 of a vector outside exact mode is recorded, not launched (pending_fill.h): the
+  // next entry point stores it, unless it is one that overwrites or consumes it.  -0.0 and short
+  // vectors keep the eager launch (fill_now validates x for that path).
+  if (ctx->defer_fill && n > 0 && alpha == 0.0 && !std::signbit(alpha) && !ssp::exact_mode(ctx, n)) {
+    SSP_TRY(check_vec(x, n, "ssp_fill"));
+    ssp::FillFlusher f{ctx};
+    ctx->pending_fills.insert(x, n, f);
+    return f.status;
+  }
+  SSP_TRY(ssp::overwrite_fills(ctx, x, n));
+  return ssp::fill_now(ctx, alpha, x, n);
 }
 
 int ssp_scal(ssp_ctx* ctx, double alpha, double* x, size_t n) {
@@ -382,11 +430,15 @@ int ssp_scal(ssp_ctx* ctx, double alpha, double* x, size_t n) {
 
 namespace {
 int copy_impl(ssp_ctx* ctx, double alpha, double* x, const double* y, size_t n, bool scaled, const char* what) {
-  SSP_CHECK_CTX(ctx);
+  SSP_CHECK_CTX_KEEP_FILLS(ctx);
   SSP_TRY(check_vec(x, n, what));
   SSP_TRY(check_vec(y, n, what));
   if (n == 0 || (x == y && !scaled)) return SSP_OK;
   if (x == y) return ssp_scal(ctx, alpha, x, n);
+  // pending zero fills: the source is read, so its are stored; x is overwritten whole and never read,
+  // so the ones inside it are dropped
+  SSP_TRY(ssp::flush_fills_over(ctx, y, n));
+  SSP_TRY(ssp::overwrite_fills(ctx, x, n));
   ssp::LedgerScope ls(ctx, scaled ? "scal_copy" : "copy", 16.0 * n);
   if (n >= kWinMin) {
     const dim3 g(ssp::win_grid(ctx, n, kWinU, 16));

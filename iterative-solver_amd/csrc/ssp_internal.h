@@ -12,6 +12,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "pending_fill.h"
 #include "subspace_hip.h"
 
 // Per-operation ledger: HIP events bracket each hot-path kernel on the context's stream, with the
@@ -51,6 +52,10 @@ struct ssp_ctx {
   // host: the one-workgroup k_publish kernel (default), or with SSP_PUBLISH=copy a D2H copy of the
   // result followed by a stream write of the sequence flag (A/B: tools/latency_probe.py).
   bool publish_copy = false;
+  // Zero fills recorded instead of launched (pending_fill.h); SSP_DEFER_FILL=0: every fill is launched
+  // at once (the same-build A/B, and the eager side of tests/test_deferred_fill_gpu.py).
+  bool defer_fill = true;
+  ssp::PendingFills pending_fills;
   hipStream_t stream = nullptr;
 
   // HBM arena: freed blocks are kept by rounded size and recycled (Q vectors are created and
@@ -142,6 +147,17 @@ constexpr int kSelectTile = 2048;  // candidates sorted per workgroup in select
 int set_error(int code, const std::string& msg);
 int hip_error(hipError_t e, const char* what);
 int use_device(ssp_ctx* ctx);
+// Deferred zero fills (kernels_stream.hip).  fill_now launches k_fill under its "fill" ledger row with
+// no look at the table: the launch of an eager ssp_fill and of every flushed entry, and the fill of
+// library code that goes on to launch a reader of x in the same call.  flush_fills stores every
+// pending entry (the default prologue, SSP_CHECK_CTX); flush_fills_over the ones that share a byte
+// with [p, p + 8 n); overwrite_fills drops the ones inside that range and stores the ones partly in it.
+int fill_now(ssp_ctx* ctx, double alpha, double* x, size_t n);
+int flush_fills(ssp_ctx* ctx);
+int flush_fills_over(ssp_ctx* ctx, const void* p, size_t n);
+int overwrite_fills(ssp_ctx* ctx, const void* p, size_t n);
+// use_device, then flush_fills.
+int enter(ssp_ctx* ctx);
 int ensure_partial(ssp_ctx* ctx, size_t n_doubles);
 int ensure_result(ssp_ctx* ctx, size_t n_doubles);
 // Stages `bytes` from host into the upload ring and returns the device address the data will have;
@@ -483,7 +499,18 @@ int launch_reduce_partials(ssp_ctx* ctx, const double* partial, int nblocks, int
     if (_s != SSP_OK) return _s;   \
   } while (0)
 
+// Prologue of every entry point: the context's device made current and every pending zero fill
+// stored, so that whatever the entry point launches or copies sees the memory an eager fill would
+// have left (nothing that touched a pending range ran since its ssp_fill).
 #define SSP_CHECK_CTX(ctx)                                              \
+  do {                                                                  \
+    if (!(ctx)) return ssp::set_error(SSP_ERR_ARG, "null ssp_ctx");     \
+    SSP_TRY(ssp::enter(ctx));                                           \
+  } while (0)
+
+// The same without the flush, for the entry points that look at the table themselves: ssp_fill,
+// ssp_gemm_outer*, ssp_copy, ssp_scal_copy and ssp_free.
+#define SSP_CHECK_CTX_KEEP_FILLS(ctx)                                   \
   do {                                                                  \
     if (!(ctx)) return ssp::set_error(SSP_ERR_ARG, "null ssp_ctx");     \
     SSP_TRY(ssp::use_device(ctx));                                      \

@@ -78,6 +78,9 @@ class SyntheticProblem : public Problem<Vec, SparseP> {
     Vec t(x);
     Vec ones(m_dev, x.size());
     check(ssp_fill(ctx(), m_s.target, ones.data_wo(), ones.local_size()), "ssp_fill");
+    // a zero fill may only be recorded by the library: taking the stream stores it, since the
+    // vector's address goes on to an action that need not be the library's own
+    (void)ssp_ctx_stream(ctx());
     check(ssp_axpy(ctx(), -1.0, ones.data(), t.data_rw(), t.local_size()), "ssp_axpy");
     const double* xp[1] = {t.data()};
     double* yp[1] = {r.data_wo()};
@@ -160,6 +163,8 @@ class DenseProblem : public Problem<Vec, SparseP> {
     Vec t(x);
     Vec ones(m_dev, x.size());
     check(ssp_fill(ctx(), 1.0, ones.data_wo(), m_n), "ssp_fill");
+    // the fill's address goes on to the action: taking the stream stores a fill the library deferred
+    (void)ssp_ctx_stream(ctx());
     check(ssp_axpy(ctx(), -1.0, ones.data(), t.data_rw(), m_n), "ssp_axpy");
     const double* xp[1] = {t.data()};
     double* yp[1] = {r.data_wo()};

@@ -234,6 +234,10 @@ class Vec {
     if (!m_fill_pending || !m_block) return;
     if (m_block.use_count() > 1) m_block = std::make_shared<Block>(m_dev, m_local);
     check_status(ssp_fill(ctx(), m_fill_value, m_block->p, m_local), "ssp_fill");
+    // The library may only have recorded a zero fill.  The block's address leaves through data*(),
+    // possibly to a caller's own kernels on the stream, so the fill is stored now: taking the stream
+    // is the library's flush point.
+    (void)ssp_ctx_stream(ctx());
     m_fill_pending = false;
   }
   bool fill_pending() const { return m_fill_pending; }
