@@ -104,6 +104,17 @@ int itsolv_davidson_synth(ssp_ctx* ctx, size_t n, const sspx_synth* spec, const 
 int itsolv_diis_synth(ssp_ctx* ctx, size_t n, const sspx_synth* spec, const itsolv_options* opt, itsolv_result* out,
                       double* x_out);
 
+/* itsolv_davidson_dense / itsolv_davidson_synth with the Q space STORED in f32 (itsolv_hbm/hbm_vec_f32.h,
+ * LinearEigensystemDavidson<Vec, VecF32, SparseP> over make_handlers_q32()): R vectors, the subspace
+ * matrices and every kernel's arithmetic stay f64; a Q vector is rounded once, to nearest-even, when it
+ * is stored.  Half the HBM per Q vector and half the bytes of every pass over the Q space.  Eigenvalues
+ * move by at most about 4 eps32 |H| (first-order perturbation of the stored vectors), so convergence
+ * thresholds down to about 1e-6 |H| are meaningful; same arguments and results as the f64 entries. */
+int itsolv_davidson_dense_q32(ssp_ctx* ctx, const double* h, size_t n, const itsolv_options* opt, itsolv_result* out,
+                              double* solutions_out);
+int itsolv_davidson_synth_q32(ssp_ctx* ctx, size_t n, const sspx_synth* spec, const itsolv_options* opt,
+                              itsolv_result* out, double* solutions_out);
+
 /* DIIS on r(x) = H (x - 1) for a dense row-major H (reference test_NonLinearEquations.cpp:38-49). */
 /* LinearEquationsDavidson (reference itsolv/LinearEquationsDavidson.h): A x_r = b_r for nrhs
  * right-hand sides b (row-major nrhs x n, host), dense row-major A resident in HBM (single rank).

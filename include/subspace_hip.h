@@ -271,6 +271,51 @@ int ssp_block_update(ssp_ctx* ctx, const double* palphas, const size_t* ptr, con
                      int kp, const double* alphas, const double* const* xx, const double* xs, int k, double* const* yy,
                      const double* ys, int m, size_t n, size_t offset);
 
+/* ---- mixed precision: vectors STORED in binary32, all arithmetic in FP64 (csrc/kernels_mixed.hip).
+ *      The Q space of a solve is written once and afterwards only read; held in f32 it takes half
+ *      the HBM and half the bytes of every pass over it (itsolv_hbm/hbm_vec_f32.h).  One rule: an f32
+ *      operand is widened to f64 as it is loaded (exact); the operation then performs exactly the
+ *      arithmetic of its f64 entry point on the widened values; where the destination is f32 the f64
+ *      result is rounded once, to nearest-even, as it is stored.  So
+ *        - results into f64 destinations are bit-identical to the f64 entry point on widened operands
+ *          (ssp_scal_copy, ssp_axpy, ssp_gemm_outer[_set]_scaled: the same fma chain i = 0..k-1);
+ *        - results into f32 destinations are (float) of that f64 result.  Exception: ssp_mx_gemm_outer
+ *          into f32 destinations with k > 64 sources runs one launch per group of 64 sources, each a
+ *          read-modify-write of the f32 destinations: the sum is rounded to f32 once per group of 64;
+ *        - reductions reorder the sum as the f64 kernels do (fixed order: repeated calls give the same
+ *          bits) and, with a communicator attached, are summed over ranks exactly as ssp_gemm_inner's;
+ *        - on vectors of at most exact_max elements (ssp_ctx_set_exact_max) axpy, dot, gemm_inner and
+ *          gemm_outer widen their f32 operands into scratch f64 vectors and call the f64 entry point
+ *          (the reference's arithmetic), then round f32 destinations once;
+ *        - a result beyond the binary32 range becomes +/-inf on narrowing: scaling is the caller's concern;
+ *        - f32 fills are never deferred, and every entry point below first stores the pending f64 zero
+ *          fills of the context.
+ *      All vectors of one side of a call share that side's dtype; pointers must be 16-byte aligned.
+ *      (SSP_F64, SSP_F64) forwards to the f64 entry point.  Ledger names: copy_f32, axpy_f32, dot_f32,
+ *      fill_f32, scal_f32, gemm_inner_f32, gemm_outer_f32; bytes count 4 per f32 and 8 per f64 element. */
+typedef enum { SSP_F64 = 0, SSP_F32 = 1 } ssp_dtype;
+/* n floats from the arena of ssp_alloc (4 n bytes, 256-byte aligned) */
+int ssp_alloc_f32(ssp_ctx* ctx, size_t n, float** out);
+int ssp_free_f32(ssp_ctx* ctx, float* p);
+int ssp_upload_f32(ssp_ctx* ctx, float* dst_dev, const float* src_host, size_t n);
+int ssp_download_f32(ssp_ctx* ctx, float* dst_host, const float* src_dev, size_t n);
+/* x[:] = (float)alpha */
+int ssp_fill_f32(ssp_ctx* ctx, double alpha, float* x, size_t n);
+/* x[:] = (float)(alpha * (double)x[:]) */
+int ssp_scal_f32(ssp_ctx* ctx, double alpha, float* x, size_t n);
+/* x[:] = (tx)(ys * y[:]), the product rounded to f64 first (ys = 1: a plain convert) */
+int ssp_mx_copy(ssp_ctx* ctx, void* x, ssp_dtype tx, const void* y, ssp_dtype ty, double ys, size_t n);
+/* y[:] = (ty)fma(alpha, x[:], y[:]) */
+int ssp_mx_axpy(ssp_ctx* ctx, double alpha, const void* x, ssp_dtype tx, void* y, ssp_dtype ty, size_t n);
+int ssp_mx_dot(ssp_ctx* ctx, const void* x, ssp_dtype tx, const void* y, ssp_dtype ty, size_t n, double* out);
+/* out (m x k, row-major) = <xs[i] xx[i], ys[j] yy[j]> summed over ranks; xs / ys may be null (all 1) */
+int ssp_mx_gemm_inner(ssp_ctx* ctx, const void* const* xx, ssp_dtype tx, const double* xs, int m,
+                      const void* const* yy, ssp_dtype ty, const double* ys, int k, size_t n, double* out);
+/* yy[j] (+)= sum_i alphas[i*m + j] (xs[i] xx[i]); set != 0: the destinations are written, not read
+ * (ssp_gemm_outer_set).  No destination may alias a source. */
+int ssp_mx_gemm_outer(ssp_ctx* ctx, const double* alphas, const void* const* xx, ssp_dtype tx, const double* xs, int k,
+                      void* const* yy, ssp_dtype ty, int m, size_t n, int set);
+
 /* ---- selection: reference util/select.h:28-55, util/select_max_dot.h:166-190,
  *      DistrArray.cpp:170-276.  Local shard [offset, offset+n) of a global array.  Returns up
  *      to nsel (global index, value) pairs in ASCENDING INDEX order (std::map order), chosen

@@ -1,0 +1,848 @@
+// Mixed-precision kernels: vectors stored in binary32, arithmetic in FP64 (include/subspace_hip.h
+// "mixed precision").  An f32 operand is widened as it is loaded, the f64 result rounded once
+// (nearest-even, v_cvt_f32_f64) where the destination is f32; every fma chain is the f64 kernel's.
+//
+// Layout.  The unit of every kernel here is the QUAD, 4 consecutive elements owned by one lane: an f32
+// quad is one 16-byte access (a wave instruction covers 1 KiB contiguous), an f64 quad two 16-byte
+// accesses 16 bytes apart (the pair of wave instructions covers 2 KiB contiguous, each whole 128-byte
+// line consumed by the two back to back).  Lane l of a window owns quad p0 + l, so an f32 source and
+// an f64 destination of the same elements meet in one lane with no cross-lane traffic.
+//   gemm_outer  bytes = N (sx k + (1 or 2) sy m)      gemm_inner  bytes = N (sx m + sy k)
+// with sx, sy the storage sizes: 48 f32 sources into 8 f64 destinations move 320 N bytes where the f64
+// kernel moves 512 N.
+#include <algorithm>
+#include <cstddef>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "ssp_internal.h"
+
+namespace {
+
+using ssp::kBlock;
+
+typedef float nt_float4 __attribute__((ext_vector_type(4)));
+typedef double nt_double2 __attribute__((ext_vector_type(2)));
+
+// One quad as loaded (f32: 4 VGPRs, f64: 8), widened where it is used.
+template <typename T>
+struct Raw;
+template <>
+struct Raw<float> {
+  nt_float4 a;
+  __device__ __forceinline__ double get(int e) const { return double(a[e]); }
+};
+template <>
+struct Raw<double> {
+  nt_double2 a, b;
+  __device__ __forceinline__ double get(int e) const { return e < 2 ? a[e] : b[e - 2]; }
+};
+
+template <typename T>
+__device__ __forceinline__ Raw<T> zero_quad() {
+  Raw<T> r;
+  if constexpr (sizeof(T) == 4) r.a = nt_float4{0.f, 0.f, 0.f, 0.f};
+  else {
+    r.a = nt_double2{0., 0.};
+    r.b = nt_double2{0., 0.};
+  }
+  return r;
+}
+
+// p: the quad's first element (16-byte aligned for f32, 32 for f64).  NT: nontemporal (streamed once).
+template <bool NT, typename T>
+__device__ __forceinline__ Raw<T> ldq(const T* p) {
+  Raw<T> r;
+  if constexpr (sizeof(T) == 4) {
+    const nt_float4* q = reinterpret_cast<const nt_float4*>(p);
+    r.a = NT ? __builtin_nontemporal_load(q) : *q;
+  } else {
+    const nt_double2* q = reinterpret_cast<const nt_double2*>(p);
+    r.a = NT ? __builtin_nontemporal_load(q) : q[0];
+    r.b = NT ? __builtin_nontemporal_load(q + 1) : q[1];
+  }
+  return r;
+}
+
+// Stores 4 f64 results, rounded to T.
+template <bool NT, typename T>
+__device__ __forceinline__ void stq(T* p, const double (&v)[4]) {
+  if constexpr (sizeof(T) == 4) {
+    const nt_float4 w = {float(v[0]), float(v[1]), float(v[2]), float(v[3])};
+    nt_float4* q = reinterpret_cast<nt_float4*>(p);
+    if (NT) __builtin_nontemporal_store(w, q);
+    else *q = w;
+  } else {
+    const nt_double2 w0 = {v[0], v[1]}, w1 = {v[2], v[3]};
+    nt_double2* q = reinterpret_cast<nt_double2*>(p);
+    if (NT) {
+      __builtin_nontemporal_store(w0, q);
+      __builtin_nontemporal_store(w1, q + 1);
+    } else {
+      q[0] = w0;
+      q[1] = w1;
+    }
+  }
+}
+
+// Window shape over quads (ssp::for_windows over double2 positions): a wave covers U x 64 consecutive
+// quads of each vector per visit, then the quads past the last whole window (thread-granular), then
+// the n mod 4 last elements (one thread of workgroup 0 each).  fw(p0): the lane's first quad of a
+// window (its others are p0 + 64 u); f(p): one quad; fe(e): one element.
+template <int U, typename FW, typename F, typename FE>
+__device__ __forceinline__ void for_quads(size_t n, FW&& fw, F&& f, FE&& fe) {
+  const int lane = threadIdx.x & 63;
+  const size_t gw = size_t(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
+  const size_t nw = size_t(gridDim.x) * (kBlock / 64);
+  const size_t n4 = n >> 2, win = 64 * size_t(U), nwin = n4 / win;
+  for (size_t c = gw; c < nwin; c += nw) fw(c * win + lane);
+  for (size_t i = nwin * win + size_t(blockIdx.x) * kBlock + threadIdx.x; i < n4; i += size_t(gridDim.x) * kBlock) f(i);
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) fe(4 * n4 + threadIdx.x);
+}
+
+unsigned quad_grid(const ssp_ctx* ctx, size_t n, int u, unsigned per_cu) {
+  return ssp::stream_grid(ctx, ((n >> 2) / (64 * size_t(u)) + 1) * 64, 1, per_cu);
+}
+
+constexpr int kMxU = 4;  // 4 KiB of an f32 vector, 8 KiB of an f64 one, per wave visit
+
+// x = (TX)(ys * y)
+template <typename TX, typename TY>
+__global__ __launch_bounds__(kBlock) void k_mx_copy(TX* __restrict__ x, const TY* __restrict__ y, size_t n, double ys) {
+  for_quads<kMxU>(
+      n,
+      [&](size_t p0) {
+        Raw<TY> v[kMxU];
+#pragma unroll
+        for (int u = 0; u < kMxU; ++u) v[u] = ldq<true>(y + 4 * (p0 + 64 * u));
+#pragma unroll
+        for (int u = 0; u < kMxU; ++u) {
+          const double w[4] = {v[u].get(0) * ys, v[u].get(1) * ys, v[u].get(2) * ys, v[u].get(3) * ys};
+          stq<true>(x + 4 * (p0 + 64 * u), w);
+        }
+      },
+      [&](size_t p) {
+        const Raw<TY> v = ldq<false>(y + 4 * p);
+        const double w[4] = {v.get(0) * ys, v.get(1) * ys, v.get(2) * ys, v.get(3) * ys};
+        stq<false>(x + 4 * p, w);
+      },
+      [&](size_t e) { x[e] = TX(double(y[e]) * ys); });
+}
+
+// y = (TY)fma(alpha, x, y): the single fma of k_axpy.
+template <typename TX, typename TY>
+__global__ __launch_bounds__(kBlock) void k_mx_axpy(const TX* __restrict__ x, TY* __restrict__ y, size_t n, double alpha) {
+  for_quads<kMxU>(
+      n,
+      [&](size_t p0) {
+        Raw<TX> xv[kMxU];
+        Raw<TY> yv[kMxU];
+#pragma unroll
+        for (int u = 0; u < kMxU; ++u) xv[u] = ldq<true>(x + 4 * (p0 + 64 * u));
+#pragma unroll
+        for (int u = 0; u < kMxU; ++u) yv[u] = ldq<true>(y + 4 * (p0 + 64 * u));
+#pragma unroll
+        for (int u = 0; u < kMxU; ++u) {
+          double w[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) w[e] = fma(alpha, xv[u].get(e), yv[u].get(e));
+          stq<true>(y + 4 * (p0 + 64 * u), w);
+        }
+      },
+      [&](size_t p) {
+        const Raw<TX> xv = ldq<false>(x + 4 * p);
+        const Raw<TY> yv = ldq<false>(y + 4 * p);
+        double w[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w[e] = fma(alpha, xv.get(e), yv.get(e));
+        stq<false>(y + 4 * p, w);
+      },
+      [&](size_t e) { y[e] = TY(fma(alpha, double(x[e]), double(y[e]))); });
+}
+
+// x = (float)(alpha * x)
+__global__ __launch_bounds__(kBlock) void k_mx_scal(float* __restrict__ x, size_t n, double alpha) {
+  for_quads<kMxU>(
+      n,
+      [&](size_t p0) {
+        Raw<float> v[kMxU];
+#pragma unroll
+        for (int u = 0; u < kMxU; ++u) v[u] = ldq<true>(x + 4 * (p0 + 64 * u));
+#pragma unroll
+        for (int u = 0; u < kMxU; ++u) {
+          const double w[4] = {v[u].get(0) * alpha, v[u].get(1) * alpha, v[u].get(2) * alpha, v[u].get(3) * alpha};
+          stq<true>(x + 4 * (p0 + 64 * u), w);
+        }
+      },
+      [&](size_t p) {
+        const Raw<float> v = ldq<false>(x + 4 * p);
+        const double w[4] = {v.get(0) * alpha, v.get(1) * alpha, v.get(2) * alpha, v.get(3) * alpha};
+        stq<false>(x + 4 * p, w);
+      },
+      [&](size_t e) { x[e] = float(double(x[e]) * alpha); });
+}
+
+// x = (float)alpha: the stride shape of k_fill, one quad per lane and trip.
+__global__ __launch_bounds__(kBlock) void k_mx_fill(float* __restrict__ x, size_t n, double alpha) {
+  const size_t n4 = n >> 2, stride = size_t(gridDim.x) * kBlock;
+  const double w[4] = {alpha, alpha, alpha, alpha};
+  for (size_t i = size_t(blockIdx.x) * kBlock + threadIdx.x; i < n4; i += stride) stq<false>(x + 4 * i, w);
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) x[4 * n4 + threadIdx.x] = float(alpha);
+}
+
+// <x, y>: the shape of k_dot_partial (4 accumulators per lane, quad e into accumulator e; one partial
+// per workgroup, folded in fixed order by the last workgroup to arrive).
+template <typename TX, typename TY>
+__global__ __launch_bounds__(kBlock) void k_mx_dot(const TX* __restrict__ x, const TY* __restrict__ y, size_t n,
+                                                   double* __restrict__ partial, const ssp::FoldTail tail) {
+  double acc[4] = {0, 0, 0, 0};
+  for_quads<kMxU>(
+      n,
+      [&](size_t p0) {
+        Raw<TX> xv[kMxU];
+        Raw<TY> yv[kMxU];
+#pragma unroll
+        for (int u = 0; u < kMxU; ++u) xv[u] = ldq<true>(x + 4 * (p0 + 64 * u));
+#pragma unroll
+        for (int u = 0; u < kMxU; ++u) yv[u] = ldq<true>(y + 4 * (p0 + 64 * u));
+#pragma unroll
+        for (int u = 0; u < kMxU; ++u)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[e] = fma(xv[u].get(e), yv[u].get(e), acc[e]);
+      },
+      [&](size_t p) {
+        const Raw<TX> xv = ldq<false>(x + 4 * p);
+        const Raw<TY> yv = ldq<false>(y + 4 * p);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] = fma(xv.get(e), yv.get(e), acc[e]);
+      },
+      [&](size_t e) { acc[0] = fma(double(x[e]), double(y[e]), acc[0]); });
+  const double s = ssp::block_sum256((acc[0] + acc[1]) + (acc[2] + acc[3]));
+  if (threadIdx.x == 0) ssp::store_partial(partial + blockIdx.x, s);
+  ssp::fold_tail(partial, tail);
+}
+
+// ---- gemm_outer -----------------------------------------------------------------------------------
+struct MxOuterArgs {
+  const void* x[ssp::kOuterSrc];
+  void* y[ssp::kOuterDst];
+  int k;
+  int m;
+  size_t n;
+  const double* alpha_dev;         // k*m > kOuterAlpha: alpha[i*m + j] in device memory
+  const double* scale_dev;         // source scales [0, k) in device memory, or null (all 1)
+  double alpha[ssp::kOuterAlpha];  // alpha[i*m + j] in the argument block
+};
+static_assert(sizeof(MxOuterArgs) <= 4000, "kernel argument block too large");
+
+// yy[j] (+)= sum_i alpha(i,j) (s_i xx[i]), the shape of k_gemm_outer: each wave owns windows of U x 64
+// quads, loads a batch of sources x U quads before the fmas (8 f32 or 4 f64 sources: the same 256
+// bytes per lane in flight), and adds the sources of every destination in order i = 0..k-1.  The
+// accumulators are the widened destinations (U x M x 4 doubles per lane); an f32 destination is rounded
+// once, as it is stored.  Alphas and scales are wave-uniform reads through the constant address space.
+template <typename TX, typename TY, int M, bool SET>
+__global__ __launch_bounds__(kBlock) void k_mx_outer(const MxOuterArgs a) {
+  using cdouble = const __attribute__((address_space(4))) double;
+  using cchar = const __attribute__((address_space(4))) char;
+  cdouble* const alpha = a.alpha_dev ? (cdouble*)a.alpha_dev
+                                     : (cdouble*)((cchar*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(MxOuterArgs, alpha));
+  cdouble* const scale_p = (cdouble*)a.scale_dev;
+  const auto scale = [&](int i) { return scale_p ? scale_p[i] : 1.0; };
+  constexpr int U = M > 8 ? 1 : 2;
+  constexpr int B = sizeof(TX) == 4 ? 8 : 4;
+  const int lane = threadIdx.x & 63;
+  const size_t gw = size_t(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
+  const size_t nw = size_t(gridDim.x) * (kBlock / 64);
+  const size_t n4 = a.n >> 2, win = 64 * U;
+  for (size_t c = gw; c * win < n4; c += nw) {
+    const size_t p0 = c * win + lane;
+    bool ok[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) ok[u] = p0 + 64 * u < n4;
+    double acc[U][M][4];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int j = 0; j < M; ++j) {
+        const Raw<TY> r = (j < a.m && ok[u] && !SET) ? ldq<true>(static_cast<const TY*>(a.y[j]) + 4 * (p0 + 64 * u))
+                                                     : zero_quad<TY>();
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[u][j][e] = r.get(e);
+      }
+    const auto add = [&](int i, const Raw<TX>(&xv)[U]) {
+      const double s = scale(i);
+      double xw[U][4];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xw[u][e] = xv[u].get(e) * s;
+#pragma unroll
+      for (int j = 0; j < M; ++j) {
+        if (j < a.m) {
+          const double al = alpha[i * a.m + j];
+#pragma unroll
+          for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[u][j][e] = fma(al, xw[u][e], acc[u][j][e]);
+        }
+      }
+    };
+    int i = 0;
+    for (; i + B <= a.k; i += B) {
+      Raw<TX> xv[B][U];
+#pragma unroll
+      for (int b = 0; b < B; ++b)
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          xv[b][u] = ok[u] ? ldq<true>(static_cast<const TX*>(a.x[i + b]) + 4 * (p0 + 64 * u)) : zero_quad<TX>();
+#pragma unroll
+      for (int b = 0; b < B; ++b) add(i + b, xv[b]);
+    }
+    for (; i < a.k; ++i) {
+      Raw<TX> xv[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        xv[u] = ok[u] ? ldq<true>(static_cast<const TX*>(a.x[i]) + 4 * (p0 + 64 * u)) : zero_quad<TX>();
+      add(i, xv);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (ok[u])
+#pragma unroll
+        for (int j = 0; j < M; ++j)
+          if (j < a.m) stq<true>(static_cast<TY*>(a.y[j]) + 4 * (p0 + 64 * u), acc[u][j]);
+  }
+  // the n mod 4 last elements: thread j of workgroup 0 owns destination j
+  if ((a.n & 3) && blockIdx.x == 0 && int(threadIdx.x) < a.m) {
+    const int j = threadIdx.x;
+    TY* y = static_cast<TY*>(a.y[j]);
+    for (size_t e = 4 * n4; e < a.n; ++e) {
+      double v = SET ? 0.0 : double(y[e]);
+      for (int i = 0; i < a.k; ++i) v = fma(alpha[i * a.m + j], double(static_cast<const TX*>(a.x[i])[e]) * scale(i), v);
+      y[e] = TY(v);
+    }
+  }
+}
+
+// ---- gemm_inner -----------------------------------------------------------------------------------
+struct MxInnerArgs {
+  const void* x[ssp::kInnerRows];  // rows: MG groups of 4
+  const void* y[ssp::kInnerCols];  // columns: NG groups of 4
+  double xs[ssp::kInnerRows];
+  double ys[ssp::kInnerCols];
+  int m;
+  int k;
+  size_t n;
+  double* partial;  // [gridDim.x][m][k]
+};
+
+// The f64 MFMA tile of k_gemm_inner (v_mfma_f64_4x4x4_f64: lane l = 16k + 4b + i holds A_b[i][k] and
+// B_b[k][i], C_b[i][j] sits in lane 16i + 4b + j) over chunks of 64 elements: the 16 lanes that hold
+// one vector (same l & 3) each load the quad p = l >> 2 of the chunk -- 256 contiguous bytes of an f32
+// vector per load instruction, 512 of an f64 one per pair -- and the quad's four elements feed four
+// MFMAs (one per element; the tiles of one element are independent, so no MFMA waits for the one
+// before it).  Operands are widened and scaled (v * s, the rounding an eager scal stores) after every
+// load of the chunk is in flight.  Lanes of absent vectors read their group's first vector and feed
+// rows / columns that are never stored; whole absent groups skip their loads by a wave-uniform branch.
+template <typename TX, typename TY, int MG, int NG>
+__global__ __launch_bounds__(kBlock) void k_mx_inner(const MxInnerArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 3, p = lane >> 2;
+  const TX* xp[MG];
+  const TY* yp[NG];
+  double xsc[MG], ysc[NG];
+  bool xok[MG], yok[NG];
+#pragma unroll
+  for (int g = 0; g < MG; ++g) {
+    xok[g] = 4 * g + r < a.m;
+    xp[g] = static_cast<const TX*>(xok[g] ? a.x[4 * g + r] : a.x[4 * g < a.m ? 4 * g : 0]);
+    xsc[g] = xok[g] ? a.xs[4 * g + r] : 1.0;
+  }
+#pragma unroll
+  for (int h = 0; h < NG; ++h) {
+    yok[h] = 4 * h + r < a.k;
+    yp[h] = static_cast<const TY*>(yok[h] ? a.y[4 * h + r] : a.y[4 * h < a.k ? 4 * h : 0]);
+    ysc[h] = yok[h] ? a.ys[4 * h + r] : 1.0;
+  }
+  double acc[MG][NG];
+#pragma unroll
+  for (int g = 0; g < MG; ++g)
+#pragma unroll
+    for (int h = 0; h < NG; ++h) acc[g][h] = 0;
+
+  const size_t gw = size_t(__builtin_amdgcn_readfirstlane(int(blockIdx.x * (kBlock / 64) + wave)));
+  const size_t nw = size_t(gridDim.x) * (kBlock / 64);
+  const size_t nchunks = a.n / 64;
+  for (size_t ch = gw; ch < nchunks; ch += nw) {
+    const size_t e0 = ch * 64 + 4 * size_t(p);
+    Raw<TX> xv[MG];
+    Raw<TY> yv[NG];
+#pragma unroll
+    for (int g = 0; g < MG; ++g) xv[g] = 4 * g < a.m ? ldq<true>(xp[g] + e0) : zero_quad<TX>();
+#pragma unroll
+    for (int h = 0; h < NG; ++h) yv[h] = 4 * h < a.k ? ldq<true>(yp[h] + e0) : zero_quad<TY>();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      double xw[MG], yw[NG];
+#pragma unroll
+      for (int g = 0; g < MG; ++g) xw[g] = xv[g].get(q) * xsc[g];
+#pragma unroll
+      for (int h = 0; h < NG; ++h) yw[h] = yv[h].get(q) * ysc[h];
+#pragma unroll
+      for (int g = 0; g < MG; ++g)
+#pragma unroll
+        for (int h = 0; h < NG; ++h) acc[g][h] = __builtin_amdgcn_mfma_f64_4x4x4f64(xw[g], yw[h], acc[g][h], 0, 0, 0);
+    }
+  }
+  // Remainder [64 nchunks, n): guarded element loads, zeros past n.
+  for (size_t s = nchunks * 64 + gw * 64; s < a.n; s += nw * 64) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const size_t i = s + 4 * size_t(p) + q;
+      double xw[MG], yw[NG];
+#pragma unroll
+      for (int g = 0; g < MG; ++g) xw[g] = (xok[g] && i < a.n) ? double(xp[g][i]) * xsc[g] : 0.0;
+#pragma unroll
+      for (int h = 0; h < NG; ++h) yw[h] = (yok[h] && i < a.n) ? double(yp[h][i]) * ysc[h] : 0.0;
+#pragma unroll
+      for (int g = 0; g < MG; ++g)
+#pragma unroll
+        for (int h = 0; h < NG; ++h) acc[g][h] = __builtin_amdgcn_mfma_f64_4x4x4f64(xw[g], yw[h], acc[g][h], 0, 0, 0);
+    }
+  }
+
+  // Fold the 4 blocks (lane bits 2-3), then the 4 waves through LDS: k_gemm_inner's epilogue.
+  __shared__ double red[kBlock / 64][MG * NG][16];
+#pragma unroll
+  for (int g = 0; g < MG; ++g)
+#pragma unroll
+    for (int h = 0; h < NG; ++h) {
+      double v = acc[g][h];
+      v += __shfl_xor(v, 4, 64);
+      v += __shfl_xor(v, 8, 64);
+      if ((lane & 12) == 0) red[wave][g * NG + h][(lane >> 4) * 4 + (lane & 3)] = v;
+    }
+  __syncthreads();
+  const size_t mk = size_t(a.m) * a.k;
+  double* out = a.partial + size_t(blockIdx.x) * mk;
+  for (int s = threadIdx.x; s < MG * NG * 16; s += kBlock) {
+    const int gh = s >> 4, e = s & 15;
+    const int row = 4 * (gh / NG) + (e >> 2), col = 4 * (gh % NG) + (e & 3);
+    if (row < a.m && col < a.k) {
+      double v = red[0][gh][e];
+#pragma unroll
+      for (int w = 1; w < kBlock / 64; ++w) v += red[w][gh][e];
+      out[size_t(row) * a.k + col] = v;
+    }
+  }
+}
+
+// ---- host side ------------------------------------------------------------------------------------
+bool bad_dtype(ssp_dtype t) { return t != SSP_F64 && t != SSP_F32; }
+double esize(ssp_dtype t) { return t == SSP_F32 ? 4.0 : 8.0; }
+
+int check_vec(const void* p, size_t n, const char* what) {
+  if (n == 0) return SSP_OK;
+  if (!p) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null vector");
+  if (!ssp::aligned16(p)) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": vector not 16-byte aligned");
+  return SSP_OK;
+}
+
+int check_ptrs(const void* const* v, int count, size_t n, const char* what) {
+  if (count > 0 && !v) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null vector list");
+  for (int i = 0; i < count; ++i) SSP_TRY(check_vec(v[i], n, what));
+  if (n > 0)
+    for (int i = 0; i < count; ++i)
+      if (!v[i]) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null vector");
+  return SSP_OK;
+}
+
+// The convert launch (no ledger row of its own, no look at exact_max: a convert is the same in both).
+int convert(ssp_ctx* ctx, void* x, ssp_dtype tx, const void* y, ssp_dtype ty, double ys, size_t n) {
+  if (n == 0) return SSP_OK;
+  const dim3 g(quad_grid(ctx, n, kMxU, 16)), b(kBlock);
+  if (tx == SSP_F32 && ty == SSP_F32)
+    SSP_LAUNCH((k_mx_copy<float, float>), g, b, 0, ctx->stream, static_cast<float*>(x), static_cast<const float*>(y), n, ys);
+  else if (tx == SSP_F32)
+    SSP_LAUNCH((k_mx_copy<float, double>), g, b, 0, ctx->stream, static_cast<float*>(x), static_cast<const double*>(y), n, ys);
+  else  // (f64, f64) never reaches here: ssp_mx_copy forwards it to ssp_copy / ssp_scal_copy
+    SSP_LAUNCH((k_mx_copy<double, float>), g, b, 0, ctx->stream, static_cast<double*>(x), static_cast<const float*>(y), n, ys);
+  SSP_TRY_HIP(hipGetLastError());
+  return SSP_OK;
+}
+
+// Scratch f64 vectors of the exact path (vectors of at most exact_max elements): an f32 operand widened
+// once per distinct pointer; blocks go back to the arena when the call returns (stream-ordered reuse).
+struct Scratch {
+  ssp_ctx* ctx;
+  std::map<const void*, double*> widened;
+  std::vector<double*> blocks;
+  explicit Scratch(ssp_ctx* c) : ctx(c) {}
+  Scratch(const Scratch&) = delete;
+  Scratch& operator=(const Scratch&) = delete;
+  ~Scratch() {
+    for (double* b : blocks) (void)ssp_free(ctx, b);
+  }
+  int fresh(size_t n, double** out) {
+    SSP_TRY(ssp_alloc(ctx, n, out));
+    blocks.push_back(*out);
+    return SSP_OK;
+  }
+  int widen(const void* p, ssp_dtype t, size_t n, const double** out) {
+    if (t == SSP_F64) {
+      *out = static_cast<const double*>(p);
+      return SSP_OK;
+    }
+    auto it = widened.find(p);
+    if (it == widened.end()) {
+      double* w;
+      SSP_TRY(fresh(n, &w));
+      SSP_TRY(convert(ctx, w, SSP_F64, p, SSP_F32, 1.0, n));
+      it = widened.emplace(p, w).first;
+    }
+    *out = it->second;
+    return SSP_OK;
+  }
+};
+
+template <typename TX, typename TY, int MG>
+int launch_inner_ng(ssp_ctx* ctx, unsigned grid, const MxInnerArgs& a) {
+  const int need = (a.k + 3) / 4;
+  const dim3 g(grid), b(kBlock);
+  if (need <= 1) SSP_LAUNCH((k_mx_inner<TX, TY, MG, 1>), g, b, 0, ctx->stream, a);
+  else if (need <= 2) SSP_LAUNCH((k_mx_inner<TX, TY, MG, 2>), g, b, 0, ctx->stream, a);
+  else if (need <= 4) SSP_LAUNCH((k_mx_inner<TX, TY, MG, 4>), g, b, 0, ctx->stream, a);
+  else if (need <= 8) SSP_LAUNCH((k_mx_inner<TX, TY, MG, 8>), g, b, 0, ctx->stream, a);
+  else if (need <= 12) SSP_LAUNCH((k_mx_inner<TX, TY, MG, 12>), g, b, 0, ctx->stream, a);
+  else SSP_LAUNCH((k_mx_inner<TX, TY, MG, 16>), g, b, 0, ctx->stream, a);
+  SSP_TRY_HIP(hipGetLastError());
+  return SSP_OK;
+}
+
+template <typename TX, typename TY>
+int launch_inner_mg(ssp_ctx* ctx, unsigned grid, const MxInnerArgs& a) {
+  const int mg = (a.m + 3) / 4;
+  if (mg <= 1) return launch_inner_ng<TX, TY, 1>(ctx, grid, a);
+  if (mg <= 2) return launch_inner_ng<TX, TY, 2>(ctx, grid, a);
+  return launch_inner_ng<TX, TY, 4>(ctx, grid, a);
+}
+
+int launch_inner(ssp_ctx* ctx, unsigned grid, const MxInnerArgs& a, ssp_dtype tr, ssp_dtype tc) {
+  if (tr == SSP_F32 && tc == SSP_F32) return launch_inner_mg<float, float>(ctx, grid, a);
+  if (tr == SSP_F32) return launch_inner_mg<float, double>(ctx, grid, a);
+  return launch_inner_mg<double, float>(ctx, grid, a);
+}
+
+// One wave per chunk of 64 elements, at most ctx->inner_per_cu workgroups per CU (k_gemm_inner's grid).
+unsigned inner_grid(const ssp_ctx* ctx, size_t n) {
+  const size_t blocks = (n / 64 + 1 + 3) / 4;
+  const size_t cap = size_t(ctx->num_cus) * size_t(ctx->inner_per_cu);
+  return unsigned(std::max<size_t>(1, std::min(blocks, cap)));
+}
+
+template <typename TX, typename TY, bool SET>
+void launch_outer_m(ssp_ctx* ctx, unsigned grid, const MxOuterArgs& a) {
+  const dim3 g(grid), b(kBlock);
+  if (a.m <= 1) SSP_LAUNCH((k_mx_outer<TX, TY, 1, SET>), g, b, 0, ctx->stream, a);
+  else if (a.m <= 2) SSP_LAUNCH((k_mx_outer<TX, TY, 2, SET>), g, b, 0, ctx->stream, a);
+  else if (a.m <= 4) SSP_LAUNCH((k_mx_outer<TX, TY, 4, SET>), g, b, 0, ctx->stream, a);
+  else if (a.m <= 8) SSP_LAUNCH((k_mx_outer<TX, TY, 8, SET>), g, b, 0, ctx->stream, a);
+  else SSP_LAUNCH((k_mx_outer<TX, TY, 16, SET>), g, b, 0, ctx->stream, a);
+}
+
+template <typename TX, typename TY>
+void launch_outer_t(ssp_ctx* ctx, unsigned grid, const MxOuterArgs& a, bool set) {
+  set ? launch_outer_m<TX, TY, true>(ctx, grid, a) : launch_outer_m<TX, TY, false>(ctx, grid, a);
+}
+
+int launch_outer(ssp_ctx* ctx, const MxOuterArgs& a, ssp_dtype tx, ssp_dtype ty, bool set) {
+  // one wave per window of 2 x 64 quads, ctx->outer_per_cu workgroups per CU (SSP_OUTER_WG_PER_CU)
+  const unsigned grid = ssp::stream_grid(ctx, a.n / 4 + 1, 2, unsigned(ctx->outer_per_cu));
+  if (tx == SSP_F32 && ty == SSP_F32) launch_outer_t<float, float>(ctx, grid, a, set);
+  else if (tx == SSP_F32) launch_outer_t<float, double>(ctx, grid, a, set);
+  else launch_outer_t<double, float>(ctx, grid, a, set);
+  SSP_TRY_HIP(hipGetLastError());
+  return SSP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ssp_alloc_f32(ssp_ctx* ctx, size_t n, float** out) {
+  if (!out) return ssp::set_error(SSP_ERR_ARG, "ssp_alloc_f32: null out");
+  double* p = nullptr;
+  SSP_TRY(ssp_alloc(ctx, (n + 1) / 2, &p));  // 4 n bytes, rounded as every block of the arena
+  *out = reinterpret_cast<float*>(p);
+  return SSP_OK;
+}
+
+int ssp_free_f32(ssp_ctx* ctx, float* p) { return ssp_free(ctx, reinterpret_cast<double*>(p)); }
+
+int ssp_upload_f32(ssp_ctx* ctx, float* dst, const float* src, size_t n) {
+  SSP_CHECK_CTX(ctx);
+  if (n == 0) return SSP_OK;
+  if (!dst || !src) return ssp::set_error(SSP_ERR_ARG, "ssp_upload_f32: null pointer");
+  SSP_TRY_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  SSP_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  return SSP_OK;
+}
+
+int ssp_download_f32(ssp_ctx* ctx, float* dst, const float* src, size_t n) {
+  SSP_CHECK_CTX(ctx);
+  if (n == 0) return SSP_OK;
+  if (!dst || !src) return ssp::set_error(SSP_ERR_ARG, "ssp_download_f32: null pointer");
+  SSP_TRY_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  SSP_TRY_HIP(hipStreamSynchronize(ctx->stream));
+  return SSP_OK;
+}
+
+int ssp_fill_f32(ssp_ctx* ctx, double alpha, float* x, size_t n) {
+  SSP_CHECK_CTX(ctx);
+  SSP_TRY(check_vec(x, n, "ssp_fill_f32"));
+  if (n == 0) return SSP_OK;
+  ssp::LedgerScope ls(ctx, "fill_f32", 4.0 * n);
+  SSP_LAUNCH(k_mx_fill, dim3(ssp::stream_grid(ctx, n / 4 + 1, 1, 64)), dim3(kBlock), 0, ctx->stream, x, n, alpha);
+  SSP_TRY_HIP(hipGetLastError());
+  return SSP_OK;
+}
+
+int ssp_scal_f32(ssp_ctx* ctx, double alpha, float* x, size_t n) {
+  SSP_CHECK_CTX(ctx);
+  SSP_TRY(check_vec(x, n, "ssp_scal_f32"));
+  if (n == 0) return SSP_OK;
+  ssp::LedgerScope ls(ctx, "scal_f32", 8.0 * n);
+  SSP_LAUNCH(k_mx_scal, dim3(quad_grid(ctx, n, kMxU, 16)), dim3(kBlock), 0, ctx->stream, x, n, alpha);
+  SSP_TRY_HIP(hipGetLastError());
+  return SSP_OK;
+}
+
+int ssp_mx_copy(ssp_ctx* ctx, void* x, ssp_dtype tx, const void* y, ssp_dtype ty, double ys, size_t n) {
+  SSP_CHECK_CTX(ctx);
+  if (bad_dtype(tx) || bad_dtype(ty)) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_copy: bad dtype");
+  SSP_TRY(check_vec(x, n, "ssp_mx_copy"));
+  SSP_TRY(check_vec(y, n, "ssp_mx_copy"));
+  if (tx == SSP_F64 && ty == SSP_F64) {
+    double* xd = static_cast<double*>(x);
+    const double* yd = static_cast<const double*>(y);
+    return ys == 1.0 ? ssp_copy(ctx, xd, yd, n) : ssp_scal_copy(ctx, ys, xd, yd, n);
+  }
+  if (n == 0) return SSP_OK;
+  if (x == y) {
+    if (tx != ty) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_copy: a vector converted onto itself");
+    return ys == 1.0 ? SSP_OK : ssp_scal_f32(ctx, ys, static_cast<float*>(x), n);
+  }
+  ssp::LedgerScope ls(ctx, "copy_f32", (esize(tx) + esize(ty)) * n);
+  return convert(ctx, x, tx, y, ty, ys, n);
+}
+
+int ssp_mx_axpy(ssp_ctx* ctx, double alpha, const void* x, ssp_dtype tx, void* y, ssp_dtype ty, size_t n) {
+  SSP_CHECK_CTX(ctx);
+  if (bad_dtype(tx) || bad_dtype(ty)) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_axpy: bad dtype");
+  SSP_TRY(check_vec(x, n, "ssp_mx_axpy"));
+  SSP_TRY(check_vec(y, n, "ssp_mx_axpy"));
+  if (tx == SSP_F64 && ty == SSP_F64) return ssp_axpy(ctx, alpha, static_cast<const double*>(x), static_cast<double*>(y), n);
+  if (n == 0) return SSP_OK;
+  if (ssp::exact_mode(ctx, n)) {
+    Scratch s(ctx);
+    const double* xw;
+    SSP_TRY(s.widen(x, tx, n, &xw));
+    if (ty == SSP_F64) return ssp_axpy(ctx, alpha, xw, static_cast<double*>(y), n);
+    double* yw;
+    SSP_TRY(s.fresh(n, &yw));
+    SSP_TRY(convert(ctx, yw, SSP_F64, y, SSP_F32, 1.0, n));
+    SSP_TRY(ssp_axpy(ctx, alpha, xw, yw, n));
+    return convert(ctx, y, SSP_F32, yw, SSP_F64, 1.0, n);
+  }
+  ssp::LedgerScope ls(ctx, "axpy_f32", (esize(tx) + 2 * esize(ty)) * n);
+  const dim3 g(quad_grid(ctx, n, kMxU, 16)), b(kBlock);
+  if (tx == SSP_F32 && ty == SSP_F32)
+    SSP_LAUNCH((k_mx_axpy<float, float>), g, b, 0, ctx->stream, static_cast<const float*>(x), static_cast<float*>(y), n, alpha);
+  else if (tx == SSP_F32)
+    SSP_LAUNCH((k_mx_axpy<float, double>), g, b, 0, ctx->stream, static_cast<const float*>(x), static_cast<double*>(y), n, alpha);
+  else
+    SSP_LAUNCH((k_mx_axpy<double, float>), g, b, 0, ctx->stream, static_cast<const double*>(x), static_cast<float*>(y), n, alpha);
+  SSP_TRY_HIP(hipGetLastError());
+  return SSP_OK;
+}
+
+int ssp_mx_dot(ssp_ctx* ctx, const void* x, ssp_dtype tx, const void* y, ssp_dtype ty, size_t n, double* out) {
+  SSP_CHECK_CTX(ctx);
+  if (bad_dtype(tx) || bad_dtype(ty)) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_dot: bad dtype");
+  if (!out) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_dot: null out");
+  SSP_TRY(check_vec(x, n, "ssp_mx_dot"));
+  SSP_TRY(check_vec(y, n, "ssp_mx_dot"));
+  if ((tx == SSP_F64 && ty == SSP_F64) || n == 0)  // n = 0: the f64 entry's zero, reduced over ranks
+    return ssp_dot(ctx, static_cast<const double*>(x), static_cast<const double*>(y), n, out);
+  if (ssp::exact_mode(ctx, n)) {
+    Scratch s(ctx);
+    const double *xw, *yw;
+    SSP_TRY(s.widen(x, tx, n, &xw));
+    SSP_TRY(s.widen(y, ty, n, &yw));
+    return ssp_dot(ctx, xw, yw, n, out);
+  }
+  const unsigned grid = quad_grid(ctx, n, kMxU, 8);
+  SSP_TRY(ssp::ensure_partial(ctx, grid));
+  ssp::FoldTail tail{};
+  SSP_TRY(ssp::fold_begin(ctx, 1, &tail));
+  {
+    ssp::LedgerScope ls(ctx, "dot_f32", (esize(tx) + esize(ty)) * n);
+    const dim3 g(grid), b(kBlock);
+    double* part = ctx->partial;
+    if (tx == SSP_F32 && ty == SSP_F32)
+      SSP_LAUNCH((k_mx_dot<float, float>), g, b, 0, ctx->stream, static_cast<const float*>(x), static_cast<const float*>(y), n, part, tail);
+    else if (tx == SSP_F32)
+      SSP_LAUNCH((k_mx_dot<float, double>), g, b, 0, ctx->stream, static_cast<const float*>(x), static_cast<const double*>(y), n, part, tail);
+    else
+      SSP_LAUNCH((k_mx_dot<double, float>), g, b, 0, ctx->stream, static_cast<const double*>(x), static_cast<const float*>(y), n, part, tail);
+    SSP_TRY_HIP(hipGetLastError());
+  }
+  return ssp::fold_finish(ctx, tail, out);
+}
+
+int ssp_mx_gemm_inner(ssp_ctx* ctx, const void* const* xx, ssp_dtype tx, const double* xs, int m,
+                      const void* const* yy, ssp_dtype ty, const double* ys, int k, size_t n, double* out) {
+  SSP_CHECK_CTX(ctx);
+  if (bad_dtype(tx) || bad_dtype(ty)) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_gemm_inner: bad dtype");
+  if (m < 0 || k < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_gemm_inner: negative dimension");
+  if (m * k > 0 && !out) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_gemm_inner: null out");
+  if (m == 0 || k == 0) return SSP_OK;
+  SSP_TRY(check_ptrs(xx, m, n, "ssp_mx_gemm_inner"));
+  SSP_TRY(check_ptrs(yy, k, n, "ssp_mx_gemm_inner"));
+  if ((tx == SSP_F64 && ty == SSP_F64) || n == 0)  // n = 0: the f64 entry's zeros, reduced over ranks
+    return ssp_gemm_inner_scaled(ctx, reinterpret_cast<const double* const*>(xx), xs, m,
+                                 reinterpret_cast<const double* const*>(yy), ys, k, n, out);
+  if (ssp::exact_mode(ctx, n)) {
+    Scratch s(ctx);
+    std::vector<const double*> xw(static_cast<size_t>(m)), yw(static_cast<size_t>(k));
+    for (int i = 0; i < m; ++i) SSP_TRY(s.widen(xx[i], tx, n, &xw[size_t(i)]));
+    for (int j = 0; j < k; ++j) SSP_TRY(s.widen(yy[j], ty, n, &yw[size_t(j)]));
+    return ssp_gemm_inner_scaled(ctx, xw.data(), xs, m, yw.data(), ys, k, n, out);
+  }
+  // The shorter side on the MFMA rows (at most 16 per launch), the longer on the columns (at most 64):
+  // the chunking of ssp_gemm_inner, the same result layout for the reduction over ranks.
+  const bool swap = m > k;
+  const void* const* rows = swap ? yy : xx;
+  const void* const* cols = swap ? xx : yy;
+  const ssp_dtype tr = swap ? ty : tx, tc = swap ? tx : ty;
+  const int R = swap ? k : m, C = swap ? m : k;
+  std::vector<double> rs(size_t(R), 1.0), cs(size_t(C), 1.0);
+  for (int i = 0; i < m; ++i) (swap ? cs : rs)[size_t(i)] = xs ? xs[i] : 1.0;
+  for (int j = 0; j < k; ++j) (swap ? rs : cs)[size_t(j)] = ys ? ys[j] : 1.0;
+  const size_t total = size_t(R) * C;
+  ssp::FoldTail tail{};
+  SSP_TRY(ssp::fold_begin(ctx, int(total), &tail));
+  {
+    ssp::LedgerScope ls(ctx, "gemm_inner_f32", (esize(tx) * m + esize(ty) * k) * n);
+    const unsigned grid = inner_grid(ctx, n);
+    for (int r0 = 0; r0 < R; r0 += ssp::kInnerRows) {
+      for (int c0 = 0; c0 < C; c0 += ssp::kInnerCols) {
+        MxInnerArgs a{};
+        a.m = std::min(ssp::kInnerRows, R - r0);
+        a.k = std::min(ssp::kInnerCols, C - c0);
+        a.n = n;
+        for (int i = 0; i < a.m; ++i) {
+          a.x[i] = rows[r0 + i];
+          a.xs[i] = rs[size_t(r0 + i)];
+        }
+        for (int j = 0; j < a.k; ++j) {
+          a.y[j] = cols[c0 + j];
+          a.ys[j] = cs[size_t(c0 + j)];
+        }
+        SSP_TRY(ssp::ensure_partial(ctx, size_t(grid) * a.m * a.k));
+        a.partial = ctx->partial;
+        SSP_TRY(launch_inner(ctx, grid, a, tr, tc));
+        const bool last = r0 + ssp::kInnerRows >= R && c0 + ssp::kInnerCols >= C;
+        SSP_TRY(ssp::launch_reduce_partials(ctx, ctx->partial, int(grid), a.m, a.k, ctx->result_dev, C, r0, c0, &tail, last));
+      }
+    }
+  }
+  std::vector<double> t(swap ? total : 0);
+  SSP_TRY(ssp::fold_finish(ctx, tail, swap ? t.data() : out));
+  if (swap)
+    for (int i = 0; i < m; ++i)
+      for (int j = 0; j < k; ++j) out[size_t(i) * k + j] = t[size_t(j) * m + i];
+  return SSP_OK;
+}
+
+int ssp_mx_gemm_outer(ssp_ctx* ctx, const double* alphas, const void* const* xx, ssp_dtype tx, const double* xs, int k,
+                      void* const* yy, ssp_dtype ty, int m, size_t n, int set) {
+  SSP_CHECK_CTX(ctx);
+  if (bad_dtype(tx) || bad_dtype(ty)) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_gemm_outer: bad dtype");
+  if (m < 0 || k < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_gemm_outer: negative dimension");
+  if (tx == SSP_F64 && ty == SSP_F64) {
+    const double* const* xd = reinterpret_cast<const double* const*>(xx);
+    double* const* yd = reinterpret_cast<double* const*>(yy);
+    return set ? ssp_gemm_outer_set_scaled(ctx, alphas, xd, xs, k, yd, m, n)
+               : ssp_gemm_outer_scaled(ctx, alphas, xd, xs, k, yd, nullptr, m, n);
+  }
+  SSP_TRY(check_ptrs(xx, k, n, "ssp_mx_gemm_outer"));
+  SSP_TRY(check_ptrs(const_cast<const void* const*>(yy), m, n, "ssp_mx_gemm_outer"));
+  if (m == 0 || n == 0) return SSP_OK;
+  if (k == 0) {
+    for (int j = 0; set && j < m; ++j) {
+      if (ty == SSP_F32) SSP_TRY(ssp_fill_f32(ctx, 0.0, static_cast<float*>(yy[j]), n));
+      else SSP_TRY(ssp_fill(ctx, 0.0, static_cast<double*>(yy[j]), n));
+    }
+    return SSP_OK;
+  }
+  if (!alphas) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_gemm_outer: null alphas");
+  for (int j = 0; j < m; ++j)
+    for (int i = 0; i < k; ++i)
+      if (yy[j] == xx[i]) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_gemm_outer: a destination aliases a source");
+  if (ssp::exact_mode(ctx, n)) {
+    Scratch s(ctx);
+    std::vector<const double*> xw(static_cast<size_t>(k));
+    std::vector<double*> yw(static_cast<size_t>(m));
+    for (int i = 0; i < k; ++i) SSP_TRY(s.widen(xx[i], tx, n, &xw[size_t(i)]));
+    for (int j = 0; j < m; ++j) {
+      if (ty == SSP_F64) {
+        yw[size_t(j)] = static_cast<double*>(yy[j]);
+        continue;
+      }
+      SSP_TRY(s.fresh(n, &yw[size_t(j)]));
+      if (!set) SSP_TRY(convert(ctx, yw[size_t(j)], SSP_F64, yy[j], SSP_F32, 1.0, n));
+    }
+    SSP_TRY(set ? ssp_gemm_outer_set_scaled(ctx, alphas, xw.data(), xs, k, yw.data(), m, n)
+                : ssp_gemm_outer_scaled(ctx, alphas, xw.data(), xs, k, yw.data(), nullptr, m, n));
+    for (int j = 0; ty == SSP_F32 && j < m; ++j) SSP_TRY(convert(ctx, yy[j], SSP_F32, yw[size_t(j)], SSP_F64, 1.0, n));
+    return SSP_OK;
+  }
+  // Destinations are independent; sources are applied in increasing order, kOuterSrc per launch, so
+  // each destination sees the reference's summation order (an f32 destination is rounded per launch).
+  ssp::LedgerScope ls(ctx, "gemm_outer_f32", (esize(tx) * k + (set ? 1.0 : 2.0) * esize(ty) * m) * n);
+  bool scaled = false;
+  for (int i = 0; xs && i < k; ++i) scaled = scaled || xs[i] != 1.0;
+  for (int j0 = 0; j0 < m; j0 += ssp::kOuterDst) {
+    const int mm = std::min(ssp::kOuterDst, m - j0);
+    for (int i0 = 0; i0 < k; i0 += ssp::kOuterSrc) {
+      MxOuterArgs a{};
+      a.m = mm;
+      a.k = std::min(ssp::kOuterSrc, k - i0);
+      a.n = n;
+      for (int i = 0; i < a.k; ++i) a.x[i] = xx[i0 + i];
+      for (int j = 0; j < mm; ++j) a.y[j] = yy[j0 + j];
+      if (scaled) {
+        void* ps;
+        SSP_TRY(ssp::upload_small(ctx, xs + i0, size_t(a.k) * sizeof(double), &ps));
+        a.scale_dev = static_cast<const double*>(ps);
+      }
+      const bool dev = a.k * mm > ssp::kOuterAlpha;
+      std::vector<double> block(dev ? size_t(a.k) * mm : 0);
+      double* dst = dev ? block.data() : a.alpha;
+      for (int i = 0; i < a.k; ++i)
+        for (int j = 0; j < mm; ++j) dst[i * mm + j] = alphas[size_t(i0 + i) * m + j0 + j];
+      if (dev) {
+        void* p;
+        SSP_TRY(ssp::upload_small(ctx, block.data(), block.size() * sizeof(double), &p));
+        a.alpha_dev = static_cast<const double*>(p);
+      }
+      SSP_TRY(ssp::flush_uploads(ctx));
+      SSP_TRY(launch_outer(ctx, a, tx, ty, set && i0 == 0));
+    }
+  }
+  return SSP_OK;
+}
+
+}  // extern "C"

@@ -20,7 +20,11 @@ EXPORTS = [
     "itsolv_last_error", "itsolv_default_options", "itsolv_davidson_synthetic", "itsolv_davidson_dense",
     "itsolv_diis_synthetic", "itsolv_diis_dense", "itsolv_linear_equations_dense", "itsolv_optimize_dense",
     "itsolv_davidson_synth", "itsolv_diis_synth",
+    # Davidson with the Q space stored in f32 (itsolv_hbm/hbm_vec_f32.h)
+    "itsolv_davidson_dense_q32", "itsolv_davidson_synth_q32",
 ]
+# Absent from the CPU emulation of the library (loaded through this binding by patching LIB_PATH).
+OPTIONAL = frozenset(n for n in EXPORTS if n.endswith("_q32"))
 
 # Diagonal families of the synthetic H (include/subspace_hip.h sspx_synth, itsolv_hbm/problems.h).
 DIAG_LINEAR, DIAG_BOUNDED = 0, 1
@@ -145,13 +149,27 @@ def load_library():
             "itsolv_optimize_dense": (I, [P, PD, Z, I, PO, PR, PD]),
             "itsolv_davidson_synth": (I, [P, Z, C.POINTER(Synth), PO, PR, PD]),
             "itsolv_diis_synth": (I, [P, Z, C.POINTER(Synth), PO, PR, PD]),
+            "itsolv_davidson_dense_q32": (I, [P, PD, Z, PO, PR, PD]),
+            "itsolv_davidson_synth_q32": (I, [P, Z, C.POINTER(Synth), PO, PR, PD]),
         }
         for name, (res, args) in sig.items():
+            if name in OPTIONAL and not hasattr(L, name):
+                continue
             f = getattr(L, name)
             f.restype = res
             f.argtypes = args
         _lib = L
     return _lib
+
+
+def _entry(name: str, q32: bool):
+    """The solver entry point `name`, or with q32 its form over a Q space stored in f32."""
+    if not q32:
+        return getattr(load_library(), name)
+    f = getattr(load_library(), name + "_q32", None)
+    if f is None:
+        raise sh.SspError(7, f"{name}_q32: the loaded library has no f32 Q space")
+    return f
 
 
 def _call(fn, args, nout):
@@ -167,22 +185,24 @@ def _call(fn, args, nout):
 
 def davidson_synthetic(ctx: sh.Context, n: int, rho: float, rank: int, seed: int, n_local: int | None = None,
                        solutions: bool = True, *, diag_kind: int = DIAG_LINEAR, alpha: float = 0.0,
-                       target: float = 1.0, **opts):
+                       target: float = 1.0, q32: bool = False, **opts):
+    """q32: the Q space is stored in f32 (half the HBM and bytes of every pass over it; arithmetic in f64)."""
     o = make_options(**opts)
     nl = n if n_local is None else n_local
     spec = Synth(rho, rank, seed, diag_kind, alpha, target)
-    r, sol = _call(load_library().itsolv_davidson_synth, (ctx.handle, n, C.byref(spec), C.byref(o)),
+    r, sol = _call(_entry("itsolv_davidson_synth", q32), (ctx.handle, n, C.byref(spec), C.byref(o)),
                    o.nroots * nl if solutions else 0)
     if solutions:
         r["solutions"] = sol[: o.nroots * nl].reshape(o.nroots, nl)
     return r
 
 
-def davidson_dense(ctx: sh.Context, h: np.ndarray, **opts):
+def davidson_dense(ctx: sh.Context, h: np.ndarray, q32: bool = False, **opts):
+    """q32: the Q space is stored in f32 (arithmetic in f64)."""
     h = np.ascontiguousarray(h, dtype=np.float64)
     n = h.shape[0]
     o = make_options(**opts)
-    r, sol = _call(load_library().itsolv_davidson_dense,
+    r, sol = _call(_entry("itsolv_davidson_dense", q32),
                    (ctx.handle, h.ctypes.data_as(C.POINTER(C.c_double)), n, C.byref(o)), o.nroots * n)
     r["solutions"] = sol[: o.nroots * n].reshape(o.nroots, n)
     return r

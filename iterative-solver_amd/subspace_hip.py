@@ -49,7 +49,16 @@ EXPORTS = [
     "sspx_synth_action_scaled",
     # a sparse inner product queued ahead of other work
     "ssp_gemm_inner_sparse_begin", "ssp_gemm_inner_sparse_end",
+    # vectors stored in f32, arithmetic in f64
+    "ssp_alloc_f32", "ssp_free_f32", "ssp_upload_f32", "ssp_download_f32", "ssp_fill_f32", "ssp_scal_f32",
+    "ssp_mx_copy", "ssp_mx_axpy", "ssp_mx_dot", "ssp_mx_gemm_inner", "ssp_mx_gemm_outer",
 ]
+
+# The mixed-precision entry points are optional in a loaded library: the CPU emulation of the f64 C ABI
+# (loaded through these bindings by patching LIB_PATH) does not have them, and a call then raises
+# SspError(SSP_ERR_UNSUPPORTED).
+OPTIONAL = frozenset(n for n in EXPORTS if n.endswith("_f32") or n.startswith("ssp_mx_"))
+SSP_F64, SSP_F32 = 0, 1
 
 
 class SspError(RuntimeError):
@@ -163,8 +172,21 @@ def _declare(lib):
         "ssp_construct_solution_scaled": (I, [P, PD, PZ, PZ, PD, I, PD, P, PD, I, P, I, Z, Z]),
         "ssp_block_update": (I, [P, PD, PZ, PZ, PD, I, PD, P, PD, I, P, PD, I, Z, Z]),
         "sspx_synth_action_scaled": (I, [P, P, P, PD, P, I, Z, Z]),
+        "ssp_alloc_f32": (I, [P, Z, C.POINTER(P)]),
+        "ssp_free_f32": (I, [P, P]),
+        "ssp_upload_f32": (I, [P, P, P, Z]),
+        "ssp_download_f32": (I, [P, P, P, Z]),
+        "ssp_fill_f32": (I, [P, D, P, Z]),
+        "ssp_scal_f32": (I, [P, D, P, Z]),
+        "ssp_mx_copy": (I, [P, P, I, P, I, D, Z]),
+        "ssp_mx_axpy": (I, [P, D, P, I, P, I, Z]),
+        "ssp_mx_dot": (I, [P, P, I, P, I, Z, PD]),
+        "ssp_mx_gemm_inner": (I, [P, P, I, PD, I, P, I, PD, I, Z, PD]),
+        "ssp_mx_gemm_outer": (I, [P, PD, P, I, PD, I, P, I, I, Z, I]),
     }
     for name, (res, args) in sig.items():
+        if name in OPTIONAL and not hasattr(lib, name):
+            continue
         f = getattr(lib, name)
         f.restype = res
         f.argtypes = args
@@ -361,15 +383,37 @@ def _zptr(a: np.ndarray):
     return a.ctypes.data_as(PZ)
 
 
-class DeviceVector:
-    """One HBM shard of n doubles, owned by a Context's arena."""
+def _dtype(dtype) -> np.dtype:
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise TypeError(f"device vectors are float64 or float32, not {dt}")
+    return dt
 
-    def __init__(self, ctx: "Context", n: int, ptr: int, owner: bool = True):
+
+def _code(v: "DeviceVector") -> int:
+    return SSP_F32 if v.dtype == np.float32 else SSP_F64
+
+
+def _same_dtype(vecs: Sequence["DeviceVector"]) -> int:
+    codes = {_code(v) for v in vecs}
+    if len(codes) > 1:
+        raise TypeError("all vectors of one side of a call share one dtype")
+    return codes.pop() if codes else SSP_F64
+
+
+class DeviceVector:
+    """One HBM shard of n doubles (or, dtype float32, n floats), owned by a Context's arena."""
+
+    def __init__(self, ctx: "Context", n: int, ptr: int, owner: bool = True, dtype=np.float64):
         self.ctx, self.n, self.ptr, self.owner = ctx, n, ptr, owner
+        self.dtype = _dtype(dtype)
 
     def free(self):
         if self.owner and self.ptr:
-            _check(self.ctx.lib.ssp_free(self.ctx.handle, self.ptr))
+            if self.dtype == np.float32:
+                _check(self.ctx._mx("ssp_free_f32")(self.ctx.handle, self.ptr))
+            else:
+                _check(self.ctx.lib.ssp_free(self.ctx.handle, self.ptr))
         self.ptr = 0
 
     def numpy(self) -> np.ndarray:
@@ -408,25 +452,42 @@ class Context:
         _check(self.lib.ssp_synchronize(self.handle))
 
     # -- memory -----------------------------------------------------------------------------
-    def alloc(self, n: int) -> DeviceVector:
-        p = C.c_void_p()
-        _check(self.lib.ssp_alloc(self.handle, n, C.byref(p)))
-        return DeviceVector(self, n, p.value)
+    def _mx(self, name: str):
+        """A mixed-precision entry point of the loaded library (OPTIONAL: absent from the emulation)."""
+        f = getattr(self.lib, name, None)
+        if f is None:
+            raise SspError(7, f"{name}: the loaded library has no mixed-precision entry points")
+        return f
 
-    def upload(self, a: np.ndarray) -> DeviceVector:
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        v = self.alloc(a.size)
-        _check(self.lib.ssp_upload(self.handle, v.ptr, a.ctypes.data, a.size))
+    def alloc(self, n: int, dtype=np.float64) -> DeviceVector:
+        p = C.c_void_p()
+        if _dtype(dtype) == np.float32:
+            _check(self._mx("ssp_alloc_f32")(self.handle, n, C.byref(p)))
+        else:
+            _check(self.lib.ssp_alloc(self.handle, n, C.byref(p)))
+        return DeviceVector(self, n, p.value, dtype=dtype)
+
+    def upload(self, a: np.ndarray, dtype=np.float64) -> DeviceVector:
+        """A new device vector of `dtype` holding a (rounded to nearest on the host when it narrows)."""
+        a = np.ascontiguousarray(a, dtype=_dtype(dtype))
+        v = self.alloc(a.size, dtype)
+        self.upload_into(v, a)
         return v
 
     def upload_into(self, v: DeviceVector, a: np.ndarray):
-        a = np.ascontiguousarray(a, dtype=np.float64)
+        a = np.ascontiguousarray(a, dtype=v.dtype)
         assert a.size == v.n
-        _check(self.lib.ssp_upload(self.handle, v.ptr, a.ctypes.data, a.size))
+        if v.dtype == np.float32:
+            _check(self._mx("ssp_upload_f32")(self.handle, v.ptr, a.ctypes.data, a.size))
+        else:
+            _check(self.lib.ssp_upload(self.handle, v.ptr, a.ctypes.data, a.size))
 
     def download(self, v: DeviceVector) -> np.ndarray:
-        out = np.empty(v.n, dtype=np.float64)
-        _check(self.lib.ssp_download(self.handle, out.ctypes.data, v.ptr, v.n))
+        out = np.empty(v.n, dtype=v.dtype)
+        if v.dtype == np.float32:
+            _check(self._mx("ssp_download_f32")(self.handle, out.ctypes.data, v.ptr, v.n))
+        else:
+            _check(self.lib.ssp_download(self.handle, out.ctypes.data, v.ptr, v.n))
         return out
 
     def memory_stats(self):
@@ -519,10 +580,16 @@ class Context:
 
     # -- ops ----------------------------------------------------------------------------------
     def fill(self, alpha: float, x: DeviceVector):
-        _check(self.lib.ssp_fill(self.handle, alpha, x.ptr, x.n))
+        if x.dtype == np.float32:
+            _check(self._mx("ssp_fill_f32")(self.handle, alpha, x.ptr, x.n))
+        else:
+            _check(self.lib.ssp_fill(self.handle, alpha, x.ptr, x.n))
 
     def scal(self, alpha: float, x: DeviceVector):
-        _check(self.lib.ssp_scal(self.handle, alpha, x.ptr, x.n))
+        if x.dtype == np.float32:
+            _check(self._mx("ssp_scal_f32")(self.handle, alpha, x.ptr, x.n))
+        else:
+            _check(self.lib.ssp_scal(self.handle, alpha, x.ptr, x.n))
 
     def copy(self, x: DeviceVector, y: DeviceVector):
         _check(self.lib.ssp_copy(self.handle, x.ptr, y.ptr, x.n))
@@ -711,6 +778,39 @@ class Context:
         n = yy[0].n if m else 0
         _check(self.lib.ssp_gemm_outer_sparse(self.handle, _dptr(alphas), _zptr(ptr), _zptr(idx), _dptr(val), k,
                                               _ptrs(yy), m, n, offset))
+
+    # -- mixed precision (include/subspace_hip.h ssp_mx_*): f32 storage, f64 arithmetic; each call
+    #    takes its dtypes from the vectors ------------------------------------------------------------
+    def mx_copy(self, x: DeviceVector, y: DeviceVector, ys: float = 1.0):
+        """x = (x.dtype)(ys * y)"""
+        _check(self._mx("ssp_mx_copy")(self.handle, x.ptr, _code(x), y.ptr, _code(y), float(ys), x.n))
+
+    def mx_axpy(self, alpha: float, x: DeviceVector, y: DeviceVector):
+        _check(self._mx("ssp_mx_axpy")(self.handle, float(alpha), x.ptr, _code(x), y.ptr, _code(y), y.n))
+
+    def mx_dot(self, x: DeviceVector, y: DeviceVector) -> float:
+        out = C.c_double()
+        _check(self._mx("ssp_mx_dot")(self.handle, x.ptr, _code(x), y.ptr, _code(y), x.n, C.byref(out)))
+        return out.value
+
+    def mx_gemm_inner(self, xx, yy, xs=None, ys=None) -> np.ndarray:
+        f = self._mx("ssp_mx_gemm_inner")
+        m, k = len(xx), len(yy)
+        out = np.zeros((m, k))
+        a, b = self._scales(xs, m), self._scales(ys, k)
+        n = xx[0].n if m else 0
+        _check(f(self.handle, _ptrs(xx), _same_dtype(xx), _dptr(a), m, _ptrs(yy), _same_dtype(yy), _dptr(b), k, n,
+                 _dptr(out)))
+        return out
+
+    def mx_gemm_outer(self, alphas, xx, yy, xs=None, set: bool = False):
+        """yy[j] (+)= sum_i alphas[i, j] (xs[i] xx[i]); set: the destinations are written, not read."""
+        f = self._mx("ssp_mx_gemm_outer")
+        alphas = np.ascontiguousarray(alphas, dtype=np.float64).reshape(len(xx), len(yy))
+        a = self._scales(xs, len(xx))
+        n = yy[0].n if yy else 0
+        _check(f(self.handle, _dptr(alphas), _ptrs(xx), _same_dtype(xx), _dptr(a), len(xx), _ptrs(yy),
+                 _same_dtype(yy), len(yy), n, int(bool(set))))
 
     # -- deferred scal (include/subspace_hip.h *_scaled): each operand with a pending scale ---------
     @staticmethod
