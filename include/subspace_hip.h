@@ -316,6 +316,37 @@ int ssp_mx_gemm_inner(ssp_ctx* ctx, const void* const* xx, ssp_dtype tx, const d
 int ssp_mx_gemm_outer(ssp_ctx* ctx, const double* alphas, const void* const* xx, ssp_dtype tx, const double* xs, int k,
                       void* const* yy, ssp_dtype ty, int m, size_t n, int set);
 
+/* ---- fused solver passes over an f32 Q space beside f64 R vectors (itsolv_hbm/hbm_handlers_f32.h):
+ *      the mixed-precision rule above, applied per column / per source.
+ *
+ * out (m x k, row-major) = <xs[i] xx[i], ys[j] yy[j]> summed over ranks.  Rows are f64; column j is
+ * stored as ty[j] (SSP_F64 or SSP_F32), in any order.  xs / ys may be null (all 1).
+ *   - One launch per tile of 16 rows x 64 column slots reads its rows once for the columns of both types.
+ *     The columns are ordered f64 first and each type padded to whole groups of 4 (csrc/mx_cols_plan.h);
+ *     a tile that holds f32 columns only runs on ssp_mx_gemm_inner's kernel.  The result comes back in
+ *     the caller's column order.
+ *   - On vectors of at most exact_max elements the f32 columns are widened into scratch and every entry
+ *     is ssp_gemm_inner_scaled's, bit for bit; else every entry is a fixed-order sum (repeated calls give
+ *     the same bits).
+ *   - With a communicator attached the buffer summed over ranks is laid out by (m, k, ty[]) alone: the
+ *     m x slots layout on the bandwidth path, on the exact path and for an empty shard (n = 0: zeros).
+ *   - All-f64 columns forward to ssp_gemm_inner_scaled, all-f32 columns to ssp_mx_gemm_inner (their
+ *     own m x k layouts, again whatever n is); m = 0 and k = 0 return at once.
+ * Ledger name gemm_inner_cols, bytes n (8 m + the sum of the columns' element sizes). */
+int ssp_q32_gemm_inner_cols(ssp_ctx* ctx, const double* const* xx, const double* xs, int m, const void* const* yy,
+                            const ssp_dtype* ty, const double* ys, int k, size_t n, double* out);
+/* ssp_construct_solution / ssp_block_update with the dense sources stored in f32 (no source scales: an
+ * f32 vector carries none); destinations f64.  Bit-identical to the f64 entry point on widened copies of
+ * the sources, at the indices the P vectors touch too (P terms first, then the dense sources in order).
+ * Ledger: the dense pass counts as gemm_outer_f32 (4 bytes per source element), the fix-up under the f64
+ * entry points' names. */
+int ssp_q32_construct_solution(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const size_t* idx,
+                               const double* val, int kp, const double* alphas, const float* const* xx, int k,
+                               double* const* yy, int m, size_t n, size_t offset);
+int ssp_q32_block_update(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const size_t* idx, const double* val,
+                         int kp, const double* alphas, const float* const* xx, int k, double* const* yy,
+                         const double* ys, int m, size_t n, size_t offset);
+
 /* ---- selection: reference util/select.h:28-55, util/select_max_dot.h:166-190,
  *      DistrArray.cpp:170-276.  Local shard [offset, offset+n) of a global array.  Returns up
  *      to nsel (global index, value) pairs in ASCENDING INDEX order (std::map order), chosen

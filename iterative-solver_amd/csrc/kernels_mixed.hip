@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "mx_cols_plan.h"
 #include "ssp_internal.h"
 
 namespace {
@@ -232,6 +233,7 @@ struct MxOuterArgs {
   size_t n;
   const double* alpha_dev;         // k*m > kOuterAlpha: alpha[i*m + j] in device memory
   const double* scale_dev;         // source scales [0, k) in device memory, or null (all 1)
+  const double* yscale_dev;        // destination scales [0, m) in device memory, or null (all 1); not with SET
   double alpha[ssp::kOuterAlpha];  // alpha[i*m + j] in the argument block
 };
 static_assert(sizeof(MxOuterArgs) <= 4000, "kernel argument block too large");
@@ -241,6 +243,8 @@ static_assert(sizeof(MxOuterArgs) <= 4000, "kernel argument block too large");
 // bytes per lane in flight), and adds the sources of every destination in order i = 0..k-1.  The
 // accumulators are the widened destinations (U x M x 4 doubles per lane); an f32 destination is rounded
 // once, as it is stored.  Alphas and scales are wave-uniform reads through the constant address space.
+// A destination's scale (the launch of a call's first source chunk only) is applied as the destination
+// is loaded, acc = y * ys[j]: the rounding an eager scal stores, as k_gemm_outer's SC form does.
 template <typename TX, typename TY, int M, bool SET>
 __global__ __launch_bounds__(kBlock) void k_mx_outer(const MxOuterArgs a) {
   using cdouble = const __attribute__((address_space(4))) double;
@@ -249,6 +253,7 @@ __global__ __launch_bounds__(kBlock) void k_mx_outer(const MxOuterArgs a) {
                                      : (cdouble*)((cchar*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(MxOuterArgs, alpha));
   cdouble* const scale_p = (cdouble*)a.scale_dev;
   const auto scale = [&](int i) { return scale_p ? scale_p[i] : 1.0; };
+  cdouble* const yscale_p = SET ? nullptr : (cdouble*)a.yscale_dev;
   constexpr int U = M > 8 ? 1 : 2;
   constexpr int B = sizeof(TX) == 4 ? 8 : 4;
   const int lane = threadIdx.x & 63;
@@ -270,6 +275,17 @@ __global__ __launch_bounds__(kBlock) void k_mx_outer(const MxOuterArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[u][j][e] = r.get(e);
       }
+    if (yscale_p) {
+#pragma unroll
+      for (int j = 0; j < M; ++j)
+        if (j < a.m) {
+          const double ys = yscale_p[j];
+#pragma unroll
+          for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[u][j][e] *= ys;
+        }
+    }
     const auto add = [&](int i, const Raw<TX>(&xv)[U]) {
       const double s = scale(i);
       double xw[U][4];
@@ -319,6 +335,7 @@ __global__ __launch_bounds__(kBlock) void k_mx_outer(const MxOuterArgs a) {
     TY* y = static_cast<TY*>(a.y[j]);
     for (size_t e = 4 * n4; e < a.n; ++e) {
       double v = SET ? 0.0 : double(y[e]);
+      if (yscale_p) v *= yscale_p[j];
       for (int i = 0; i < a.k; ++i) v = fma(alpha[i * a.m + j], double(static_cast<const TX*>(a.x[i])[e]) * scale(i), v);
       y[e] = TY(v);
     }
@@ -405,6 +422,152 @@ __global__ __launch_bounds__(kBlock) void k_mx_inner(const MxInnerArgs a) {
       for (int g = 0; g < MG; ++g) xw[g] = (xok[g] && i < a.n) ? double(xp[g][i]) * xsc[g] : 0.0;
 #pragma unroll
       for (int h = 0; h < NG; ++h) yw[h] = (yok[h] && i < a.n) ? double(yp[h][i]) * ysc[h] : 0.0;
+#pragma unroll
+      for (int g = 0; g < MG; ++g)
+#pragma unroll
+        for (int h = 0; h < NG; ++h) acc[g][h] = __builtin_amdgcn_mfma_f64_4x4x4f64(xw[g], yw[h], acc[g][h], 0, 0, 0);
+    }
+  }
+
+  // Fold the 4 blocks (lane bits 2-3), then the 4 waves through LDS: k_gemm_inner's epilogue.
+  __shared__ double red[kBlock / 64][MG * NG][16];
+#pragma unroll
+  for (int g = 0; g < MG; ++g)
+#pragma unroll
+    for (int h = 0; h < NG; ++h) {
+      double v = acc[g][h];
+      v += __shfl_xor(v, 4, 64);
+      v += __shfl_xor(v, 8, 64);
+      if ((lane & 12) == 0) red[wave][g * NG + h][(lane >> 4) * 4 + (lane & 3)] = v;
+    }
+  __syncthreads();
+  const size_t mk = size_t(a.m) * a.k;
+  double* out = a.partial + size_t(blockIdx.x) * mk;
+  for (int s = threadIdx.x; s < MG * NG * 16; s += kBlock) {
+    const int gh = s >> 4, e = s & 15;
+    const int row = 4 * (gh / NG) + (e >> 2), col = 4 * (gh % NG) + (e & 3);
+    if (row < a.m && col < a.k) {
+      double v = red[0][gh][e];
+#pragma unroll
+      for (int w = 1; w < kBlock / 64; ++w) v += red[w][gh][e];
+      out[size_t(row) * a.k + col] = v;
+    }
+  }
+}
+
+// ---- gemm_inner over columns of both storage types ------------------------------------------------
+struct ColsInnerArgs {
+  const double* x[ssp::kInnerRows];  // rows (f64): MG groups of 4
+  const void* y[ssp::kInnerCols];    // column slots: NG groups of 4, the first g64 groups f64, the others f32;
+                                     // null: a padding slot (never the first of its group)
+  double xs[ssp::kInnerRows];
+  double ys[ssp::kInnerCols];
+  int m;
+  int k;    // slots, a multiple of 4
+  int g64;
+  size_t n;
+  double* partial;  // [gridDim.x][m][k]
+};
+static_assert(sizeof(ColsInnerArgs) <= 4000, "kernel argument block too large");
+
+
+// k_mx_inner<double, TY> with TY chosen per group of 4 columns (mx_cols_plan.h): group h of the tile is
+// f64 when h < g64, a wave-uniform branch, so one launch reads its rows once for the columns of both
+// types.  The chunk-to-wave mapping, the MFMA order (elements in increasing order per accumulator) and
+// the epilogue are k_mx_inner's.  Lanes of a padding slot read their group's first column; what they
+// accumulate is stored with the rest (the layout of the partials depends on the slots only) and dropped
+// by the host.
+// Registers: every group's quad has 16 bytes in lo[h] (an f32 quad, or the first half of an f64 one) and,
+// for the first H64 groups, the ones that can be f64, the 16 more of hi[h].  H64 = NG: any group may be
+// f64.  A lean form (H64 = 4: the 16 f64 columns of a subspace update, later groups f32 statically, the
+// register footprint of k_mx_inner<double, float>) measured no faster on the tile of 16 f64 + 48 f32
+// columns at N = 1.25e7 and 1e8 (profiles/r8/q32_fused.md), so it is not instantiated.
+template <int MG, int NG>
+__global__ __launch_bounds__(kBlock) void k_q32_inner_cols(const ColsInnerArgs a) {
+  constexpr int H64 = NG;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 3, p = lane >> 2;
+  const int g64 = a.g64;
+  const double* xp[MG];
+  const char* yp[NG];
+  double xsc[MG], ysc[NG];
+  bool xok[MG], yok[NG];
+#pragma unroll
+  for (int g = 0; g < MG; ++g) {
+    xok[g] = 4 * g + r < a.m;
+    xp[g] = xok[g] ? a.x[4 * g + r] : a.x[4 * g < a.m ? 4 * g : 0];
+    xsc[g] = xok[g] ? a.xs[4 * g + r] : 1.0;
+  }
+#pragma unroll
+  for (int h = 0; h < NG; ++h) {
+    const void* c = 4 * h < a.k ? a.y[4 * h + r] : nullptr;
+    yok[h] = c != nullptr;
+    yp[h] = static_cast<const char*>(yok[h] ? c : a.y[4 * h < a.k ? 4 * h : 0]);
+    ysc[h] = yok[h] ? a.ys[4 * h + r] : 1.0;
+  }
+  double acc[MG][NG];
+#pragma unroll
+  for (int g = 0; g < MG; ++g)
+#pragma unroll
+    for (int h = 0; h < NG; ++h) acc[g][h] = 0;
+
+  const size_t gw = size_t(__builtin_amdgcn_readfirstlane(int(blockIdx.x * (kBlock / 64) + wave)));
+  const size_t nw = size_t(gridDim.x) * (kBlock / 64);
+  const size_t nchunks = a.n / 64;
+  for (size_t ch = gw; ch < nchunks; ch += nw) {
+    const size_t e0 = ch * 64 + 4 * size_t(p);
+    Raw<double> xv[MG];
+    nt_float4 lo[NG];
+    nt_double2 hi[H64];
+#pragma unroll
+    for (int g = 0; g < MG; ++g) xv[g] = 4 * g < a.m ? ldq<true>(xp[g] + e0) : zero_quad<double>();
+#pragma unroll
+    for (int h = 0; h < NG; ++h) {
+      lo[h] = nt_float4{0.f, 0.f, 0.f, 0.f};
+      if (h < H64) hi[h < H64 ? h : 0] = nt_double2{0., 0.};
+      if (4 * h < a.k) {
+        if (h < H64 && h < g64) {
+          const Raw<double> v = ldq<true>(reinterpret_cast<const double*>(yp[h]) + e0);
+          lo[h] = __builtin_bit_cast(nt_float4, v.a);
+          hi[h < H64 ? h : 0] = v.b;
+        } else {
+          lo[h] = ldq<true>(reinterpret_cast<const float*>(yp[h]) + e0).a;
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      double xw[MG], yw[NG];
+#pragma unroll
+      for (int g = 0; g < MG; ++g) xw[g] = xv[g].get(q) * xsc[g];
+#pragma unroll
+      for (int h = 0; h < NG; ++h) {
+        double v = double(lo[h][q]);
+        if (h < H64 && h < g64) v = q < 2 ? __builtin_bit_cast(nt_double2, lo[h])[q] : hi[h < H64 ? h : 0][q - 2];
+        yw[h] = v * ysc[h];
+      }
+#pragma unroll
+      for (int g = 0; g < MG; ++g)
+#pragma unroll
+        for (int h = 0; h < NG; ++h) acc[g][h] = __builtin_amdgcn_mfma_f64_4x4x4f64(xw[g], yw[h], acc[g][h], 0, 0, 0);
+    }
+  }
+  // Remainder [64 nchunks, n): guarded element loads, zeros past n.
+  for (size_t s = nchunks * 64 + gw * 64; s < a.n; s += nw * 64) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const size_t i = s + 4 * size_t(p) + q;
+      double xw[MG], yw[NG];
+#pragma unroll
+      for (int g = 0; g < MG; ++g) xw[g] = (4 * g < a.m && i < a.n) ? xp[g][i] * xsc[g] : 0.0;
+#pragma unroll
+      for (int h = 0; h < NG; ++h) {
+        double v = 0.0;
+        if (4 * h < a.k && i < a.n)
+          v = (h < H64 && h < g64) ? reinterpret_cast<const double*>(yp[h])[i]
+                                   : double(reinterpret_cast<const float*>(yp[h])[i]);
+        yw[h] = v * ysc[h];
+      }
 #pragma unroll
       for (int g = 0; g < MG; ++g)
 #pragma unroll
@@ -566,9 +729,199 @@ int launch_outer(ssp_ctx* ctx, const MxOuterArgs& a, ssp_dtype tx, ssp_dtype ty,
   return SSP_OK;
 }
 
+template <int MG>
+int launch_cols_ng(ssp_ctx* ctx, unsigned grid, const ColsInnerArgs& a) {
+  const int need = a.k / 4;
+  const dim3 g(grid), b(kBlock);
+  if (need <= 1) SSP_LAUNCH((k_q32_inner_cols<MG, 1>), g, b, 0, ctx->stream, a);
+  else if (need <= 2) SSP_LAUNCH((k_q32_inner_cols<MG, 2>), g, b, 0, ctx->stream, a);
+  else if (need <= 4) SSP_LAUNCH((k_q32_inner_cols<MG, 4>), g, b, 0, ctx->stream, a);
+  else if (need <= 8) SSP_LAUNCH((k_q32_inner_cols<MG, 8>), g, b, 0, ctx->stream, a);
+  else if (need <= 12) SSP_LAUNCH((k_q32_inner_cols<MG, 12>), g, b, 0, ctx->stream, a);
+  else SSP_LAUNCH((k_q32_inner_cols<MG, 16>), g, b, 0, ctx->stream, a);
+  SSP_TRY_HIP(hipGetLastError());
+  return SSP_OK;
+}
+
+int launch_cols(ssp_ctx* ctx, unsigned grid, const ColsInnerArgs& a) {
+  const int mg = (a.m + 3) / 4;
+  if (mg <= 1) return launch_cols_ng<1>(ctx, grid, a);
+  if (mg <= 2) return launch_cols_ng<2>(ctx, grid, a);
+  return launch_cols_ng<4>(ctx, grid, a);
+}
+
 }  // namespace
 
+namespace ssp {
+
+// The dense pass of ssp_q32_construct_solution / ssp_q32_block_update outside exact mode:
+// yy[j] = (set ? 0 : ys[j] yy[j]) + sum_i alphas(i, j) xx[i] with f32 sources and f64 destinations,
+// element for element the fma chain of ssp_gemm_outer_set_scaled / ssp_gemm_outer_scaled on widened
+// sources (k_mx_outer; the destination scales ride along with the first source chunk).
+int q32_dense_pass(ssp_ctx* ctx, const double* alphas, const float* const* xx, int k, double* const* yy,
+                   const double* ys, int m, size_t n, bool set) {
+  if (set && k == 0) {  // zero fills that may stay deferred, as ssp_gemm_outer_set's
+    for (int j = 0; j < m; ++j) SSP_TRY(ssp_fill(ctx, 0.0, yy[j], n));
+    return SSP_OK;
+  }
+  if (m == 0 || n == 0) return SSP_OK;
+  if (k == 0) {
+    for (int j = 0; j < m; ++j)
+      if (ys && ys[j] != 1.0) SSP_TRY(ssp_scal(ctx, ys[j], yy[j], n));
+    return SSP_OK;
+  }
+  if (!alphas) return set_error(SSP_ERR_ARG, "ssp_q32: null alphas");
+  for (int j = 0; j < m; ++j)
+    for (int i = 0; i < k; ++i)
+      if (static_cast<const void*>(yy[j]) == static_cast<const void*>(xx[i]))
+        return set_error(SSP_ERR_ARG, "ssp_q32: a destination aliases a source");
+  // pending zero fills: the sources are read and the read-modify-write destinations too (theirs are
+  // stored); a write-only destination's are dropped
+  if (!ctx->pending_fills.empty()) {
+    for (int i = 0; i < k; ++i) SSP_TRY(flush_fills_over(ctx, xx[i], (n + 1) / 2));
+    for (int j = 0; j < m; ++j) SSP_TRY(set ? overwrite_fills(ctx, yy[j], n) : flush_fills_over(ctx, yy[j], n));
+  }
+  LedgerScope ls(ctx, "gemm_outer_f32", (4.0 * k + (set ? 1.0 : 2.0) * 8.0 * m) * n);
+  bool scaled = false;
+  for (int j = 0; !set && ys && j < m; ++j) scaled = scaled || ys[j] != 1.0;
+  for (int j0 = 0; j0 < m; j0 += kOuterDst) {
+    const int mm = std::min(kOuterDst, m - j0);
+    for (int i0 = 0; i0 < k; i0 += kOuterSrc) {
+      MxOuterArgs a{};
+      a.m = mm;
+      a.k = std::min(kOuterSrc, k - i0);
+      a.n = n;
+      for (int i = 0; i < a.k; ++i) a.x[i] = xx[i0 + i];
+      for (int j = 0; j < mm; ++j) a.y[j] = yy[j0 + j];
+      if (scaled && i0 == 0) {
+        void* ps;
+        SSP_TRY(upload_small(ctx, ys + j0, size_t(mm) * sizeof(double), &ps));
+        a.yscale_dev = static_cast<const double*>(ps);
+      }
+      const bool dev = a.k * mm > kOuterAlpha;
+      std::vector<double> block(dev ? size_t(a.k) * mm : 0);
+      double* dst = dev ? block.data() : a.alpha;
+      for (int i = 0; i < a.k; ++i)
+        for (int j = 0; j < mm; ++j) dst[i * mm + j] = alphas[size_t(i0 + i) * m + j0 + j];
+      if (dev) {
+        void* p;
+        SSP_TRY(upload_small(ctx, block.data(), block.size() * sizeof(double), &p));
+        a.alpha_dev = static_cast<const double*>(p);
+      }
+      SSP_TRY(flush_uploads(ctx));
+      SSP_TRY(launch_outer(ctx, a, SSP_F32, SSP_F64, set && i0 == 0));
+    }
+  }
+  return SSP_OK;
+}
+
+}  // namespace ssp
+
 extern "C" {
+
+int ssp_q32_gemm_inner_cols(ssp_ctx* ctx, const double* const* xx, const double* xs, int m, const void* const* yy,
+                            const ssp_dtype* ty, const double* ys, int k, size_t n, double* out) {
+  SSP_CHECK_CTX(ctx);  // pending zero fills are stored: every operand is read
+  if (m < 0 || k < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_q32_gemm_inner_cols: negative dimension");
+  if (k > 0 && !ty) return ssp::set_error(SSP_ERR_ARG, "ssp_q32_gemm_inner_cols: null dtype list");
+  int n32 = 0;
+  for (int j = 0; j < k; ++j) {
+    if (bad_dtype(ty[j])) return ssp::set_error(SSP_ERR_ARG, "ssp_q32_gemm_inner_cols: bad dtype");
+    n32 += ty[j] == SSP_F32;
+  }
+  if (m * k > 0 && !out) return ssp::set_error(SSP_ERR_ARG, "ssp_q32_gemm_inner_cols: null out");
+  if (m == 0 || k == 0) return SSP_OK;
+  SSP_TRY(check_ptrs(reinterpret_cast<const void* const*>(xx), m, n, "ssp_q32_gemm_inner_cols"));
+  SSP_TRY(check_ptrs(yy, k, n, "ssp_q32_gemm_inner_cols"));
+  if (n32 == 0)
+    return ssp_gemm_inner_scaled(ctx, xx, xs, m, reinterpret_cast<const double* const*>(yy), ys, k, n, out);
+  if (n32 == k)  // (its n = 0 is the f64 entry's, in the same m x k layout as its other paths)
+    return ssp_mx_gemm_inner(ctx, reinterpret_cast<const void* const*>(xx), SSP_F64, xs, m, yy, SSP_F32, ys, k, n, out);
+  std::vector<unsigned char> f32(static_cast<size_t>(k));
+  for (int j = 0; j < k; ++j) f32[size_t(j)] = ty[j] == SSP_F32;
+  const ssp::ColsPlan plan = ssp::plan_cols(m, f32.data(), k, ssp::kInnerRows, ssp::kInnerCols);
+  const int S = plan.slots;
+  const size_t total = size_t(m) * S;
+  std::vector<double> rs(static_cast<size_t>(m), 1.0), cs(static_cast<size_t>(S), 1.0);
+  for (int i = 0; xs && i < m; ++i) rs[size_t(i)] = xs[i];
+  for (int j = 0; ys && j < k; ++j) cs[size_t(plan.col_slot[size_t(j)])] = ys[j];
+  double bytes = 8.0 * m;
+  for (int j = 0; j < k; ++j) bytes += esize(ty[j]);
+  std::vector<double> res(total);
+  const auto deliver = [&] {
+    for (int i = 0; i < m; ++i)
+      for (int j = 0; j < k; ++j) out[size_t(i) * k + j] = res[size_t(i) * S + size_t(plan.col_slot[size_t(j)])];
+    return SSP_OK;
+  };
+  if (n == 0) {
+    // an empty shard: zeros in the slot layout of every other path, so that the buffer summed over
+    // ranks has the layout (m, k, ty[]) give it whatever the local n is (ssp_gemm_inner_scaled's n = 0)
+    SSP_TRY(ssp::ensure_result(ctx, total));
+    SSP_TRY_HIP(hipMemsetAsync(ctx->result_dev, 0, total * sizeof(double), ctx->stream));
+    SSP_TRY(ssp::reduce_fetch(ctx, res.data(), total));
+    return deliver();
+  }
+  const bool exact = ssp::exact_mode(ctx, n);
+  Scratch scratch(ctx);
+  // exact mode: the reference's sequential dots on widened columns, in the slot layout of the bandwidth
+  // path (a padding slot repeats the first row; computed, never read back): what is summed over ranks
+  // has the same layout whichever path a rank's shard length takes.
+  std::vector<const double*> cols(static_cast<size_t>(exact ? S : 0), xx[0]);
+  for (int j = 0; exact && j < k; ++j)
+    SSP_TRY(scratch.widen(yy[j], ty[j], n, &cols[size_t(plan.col_slot[size_t(j)])]));
+  ssp::FoldTail tail{};
+  SSP_TRY(ssp::fold_begin(ctx, int(total), &tail));
+  if (exact) {
+    ssp::LedgerScope ls(ctx, "gemm_inner_cols", bytes * n);
+    SSP_TRY(ssp::exact_inner(ctx, xx, rs.data(), m, cols.data(), cs.data(), S, n, false, tail));
+  } else {
+    ssp::LedgerScope ls(ctx, "gemm_inner_cols", bytes * n);
+    const unsigned grid = inner_grid(ctx, n);
+    for (size_t t = 0; t < plan.tiles.size(); ++t) {
+      const ssp::ColsTile& tile = plan.tiles[t];
+      ColsInnerArgs a{};
+      a.m = tile.rows;
+      a.k = tile.cols;
+      a.g64 = tile.g64;
+      a.n = n;
+      for (int i = 0; i < a.m; ++i) {
+        a.x[i] = xx[tile.r0 + i];
+        a.xs[i] = rs[size_t(tile.r0 + i)];
+      }
+      for (int j = 0; j < a.k; ++j) {
+        const int col = plan.slot_col[size_t(tile.c0 + j)];
+        a.y[j] = col < 0 ? nullptr : yy[col];
+        a.ys[j] = cs[size_t(tile.c0 + j)];
+      }
+      SSP_TRY(ssp::ensure_partial(ctx, size_t(grid) * a.m * a.k));
+      a.partial = ctx->partial;
+      if (tile.g64 == 0) {
+        // a tile of f32 columns only: k_mx_inner<double, float>, the same partials (a padding slot
+        // repeats its group's first column: computed, never read back)
+        MxInnerArgs b{};
+        b.m = a.m;
+        b.k = a.k;
+        b.n = n;
+        b.partial = a.partial;
+        for (int i = 0; i < a.m; ++i) {
+          b.x[i] = a.x[i];
+          b.xs[i] = a.xs[i];
+        }
+        for (int j = 0; j < a.k; ++j) {
+          b.y[j] = a.y[j] ? a.y[j] : a.y[j & ~3];
+          b.ys[j] = a.ys[j];
+        }
+        SSP_TRY((launch_inner_mg<double, float>(ctx, grid, b)));
+      } else {
+        SSP_TRY(launch_cols(ctx, grid, a));
+      }
+      SSP_TRY(ssp::launch_reduce_partials(ctx, ctx->partial, int(grid), a.m, a.k, ctx->result_dev, S, tile.r0, tile.c0,
+                                          &tail, t + 1 == plan.tiles.size()));
+    }
+  }
+  SSP_TRY(ssp::fold_finish(ctx, tail, res.data()));
+  return deliver();
+}
 
 int ssp_alloc_f32(ssp_ctx* ctx, size_t n, float** out) {
   if (!out) return ssp::set_error(SSP_ERR_ARG, "ssp_alloc_f32: null out");

@@ -173,7 +173,8 @@ __global__ void k_sparse_outer(const SparseOuterArgs a) {
 // order, the arithmetic of k_gemm_outer.
 // rmw (ssp_block_update): the destinations are read -- v starts from the value saved before the
 // dense pass times the destination's deferred scale instead of 0.  xs: the dense sources' deferred
-// scales (null: 1).
+// scales (null: 1).  TX: the storage type of the dense sources (float: widened as they are loaded).
+template <typename TX>
 struct ConstructFixArgs {
   const double* saved;             // rmw: [u * m + j] = yy[j][uidx[u]] before the dense pass
   const double* ys;                // rmw: m destination scales
@@ -191,7 +192,7 @@ struct ConstructFixArgs {
   int entries;                     // ptr[kp]
   const double* palpha;            // kp x m
   const double* alpha;             // k x m
-  const double* const* x;          // k dense sources
+  const TX* const* x;              // k dense sources
   double* const* y;                // m destinations
 };
 
@@ -199,12 +200,13 @@ struct ConstructFixArgs {
 // pointers) are staged in LDS first: one round of parallel loads instead of a chain of dependent
 // global loads per P entry (17.8 -> ~6 us a launch at the C4 shard).  Larger operands read global.
 constexpr int kFixEntries = 512, kFixP = 64, kFixPalpha = 1024, kFixSrc = 128;
-__global__ __launch_bounds__(256) void k_construct_fixup(const ConstructFixArgs a) {
+template <typename TX>
+__global__ __launch_bounds__(256) void k_construct_fixup(const ConstructFixArgs<TX> a) {
   __shared__ unsigned long long s_ptr[kFixP + 1];
   __shared__ unsigned long long s_li[kFixEntries];
   __shared__ double s_v[kFixEntries];
   __shared__ double s_pal[kFixPalpha];
-  __shared__ const double* s_x[kFixSrc];
+  __shared__ const TX* s_x[kFixSrc];
   const bool staged = a.kp <= kFixP && a.entries <= kFixEntries && size_t(a.kp) * a.m <= kFixPalpha && a.k <= kFixSrc;
   if (staged) {
     for (int q = int(threadIdx.x); q <= a.kp; q += int(blockDim.x)) s_ptr[q] = a.ptr[q];
@@ -220,7 +222,7 @@ __global__ __launch_bounds__(256) void k_construct_fixup(const ConstructFixArgs 
   const unsigned long long* li = staged ? s_li : a.li;
   const double* pv = staged ? s_v : a.v;
   const double* pal = staged ? s_pal : a.palpha;
-  const double* const* xsrc = staged ? s_x : a.x;
+  const TX* const* xsrc = staged ? s_x : a.x;
   const size_t t = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= a.nu * size_t(a.m)) return;
   const size_t u = t / a.m;
@@ -241,7 +243,7 @@ __global__ __launch_bounds__(256) void k_construct_fixup(const ConstructFixArgs 
 #pragma unroll
     for (int u = 0; u < G; ++u) {
       const int s = min(s0 + u, a.k - 1);
-      xv[u] = xsrc[s][g];
+      xv[u] = double(xsrc[s][g]);
       al[u] = a.alpha[size_t(s) * a.m + j];
     }
     if (a.xs) {
@@ -634,10 +636,13 @@ int ssp_gemm_outer_sparse(ssp_ctx* ctx, const double* alphas, const size_t* ptr,
 namespace {
 // construct_solution (rmw = false: destinations written without being read) and the block update
 // (rmw = true: yy[j] = ys[j] yy[j] + P + dense): the dense pass over every element, then the fix-up
-// that recomputes the indices the P vectors touch in the reference's order (P first).
+// that recomputes the indices the P vectors touch in the reference's order (P first).  TX: the dense
+// sources' storage type; dense(): the dense pass over them (the gather before it and the fix-up after it
+// are the same for both).
+template <typename TX, typename Dense>
 int solution_impl(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const size_t* idx, const double* val,
-                  int kp, const double* alphas, const double* const* xx, const double* xs, int k, double* const* yy,
-                  const double* ys, int m, size_t n, size_t offset, bool rmw, const char* what) {
+                  int kp, const double* alphas, const TX* const* xx, const double* xs, int k, double* const* yy,
+                  const double* ys, int m, size_t n, size_t offset, bool rmw, const char* what, Dense&& dense) {
   SSP_CHECK_CTX(ctx);
   if (m < 0 || k < 0 || kp < 0) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": negative dimension");
   if (m == 0) return SSP_OK;
@@ -667,15 +672,12 @@ int solution_impl(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const 
     SSP_TRY_HIP(hipGetLastError());
     saved = ctx->partial;  // nothing below resizes the partials workspace before the fix-up reads it
   }
-  if (rmw)
-    SSP_TRY(ssp_gemm_outer_scaled(ctx, alphas, xx, xs, k, yy, ys, m, n));
-  else
-    SSP_TRY(ssp_gemm_outer_set_scaled(ctx, alphas, xx, xs, k, yy, m, n));
+  SSP_TRY(dense());
   if (uidx.empty()) return SSP_OK;
   // with no dense source the write-only pass above is m deferred zero fills: the fix-up below writes
   // into those vectors, so they are stored first
   SSP_TRY(ssp::flush_fills(ctx));
-  ConstructFixArgs a{};
+  ConstructFixArgs<TX> a{};
   unsigned long long *dptr, *dli;
   double* dv;
   SSP_TRY(upload_entries(ctx, lptr, li, lv, &dptr, &dli, &dv));
@@ -690,8 +692,8 @@ int solution_impl(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const 
   if (k > 0) {
     SSP_TRY(ssp::upload_small(ctx, alphas, size_t(k) * m * sizeof(double), &p));
     a.alpha = static_cast<const double*>(p);
-    SSP_TRY(ssp::upload_small(ctx, xx, size_t(k) * sizeof(double*), &p));
-    a.x = static_cast<const double* const*>(p);
+    SSP_TRY(ssp::upload_small(ctx, xx, size_t(k) * sizeof(TX*), &p));
+    a.x = static_cast<const TX* const*>(p);
     if (xs) {
       SSP_TRY(ssp::upload_small(ctx, xs, size_t(k) * sizeof(double), &p));
       a.xs = static_cast<const double*>(p);
@@ -718,9 +720,52 @@ int solution_impl(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const 
                       8.0 * a.nu * m * (2.0 + k + (rmw ? 1.0 : 0.0)));
   const size_t threads = a.nu * size_t(m);
   SSP_TRY(ssp::flush_uploads(ctx));
-  SSP_LAUNCH(k_construct_fixup, dim3(unsigned((threads + 255) / 256)), dim3(256), 0, ctx->stream, a);
+  SSP_LAUNCH(k_construct_fixup<TX>, dim3(unsigned((threads + 255) / 256)), dim3(256), 0, ctx->stream, a);
   SSP_TRY_HIP(hipGetLastError());
   return SSP_OK;
+}
+
+// f64 sources: the dense pass is ssp_gemm_outer_scaled / ssp_gemm_outer_set_scaled.
+int solution_f64(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const size_t* idx, const double* val, int kp,
+                 const double* alphas, const double* const* xx, const double* xs, int k, double* const* yy,
+                 const double* ys, int m, size_t n, size_t offset, bool rmw, const char* what) {
+  return solution_impl(ctx, palphas, ptr, idx, val, kp, alphas, xx, xs, k, yy, ys, m, n, offset, rmw, what, [&] {
+    return rmw ? ssp_gemm_outer_scaled(ctx, alphas, xx, xs, k, yy, ys, m, n)
+               : ssp_gemm_outer_set_scaled(ctx, alphas, xx, xs, k, yy, m, n);
+  });
+}
+
+// f32 sources.  On vectors of at most exact_max elements the sources are widened into scratch and the
+// call is the f64 one; else the dense pass reads them as stored (ssp::q32_dense_pass) and the fix-up
+// widens the few elements it reads: bit for bit the f64 call on widened copies either way.
+int solution_f32(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const size_t* idx, const double* val, int kp,
+                 const double* alphas, const float* const* xx, int k, double* const* yy, const double* ys, int m,
+                 size_t n, size_t offset, bool rmw, const char* what) {
+  if (!ctx) return ssp::set_error(SSP_ERR_ARG, "null ssp_ctx");
+  if (m < 0 || k < 0 || kp < 0) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": negative dimension");
+  if ((k > 0 && !xx) || (m > 0 && !yy)) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null vector list");
+  for (int i = 0; n > 0 && i < k; ++i)
+    if (!xx[i] || !ssp::aligned16(xx[i]))
+      return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null or misaligned source");
+  for (int j = 0; n > 0 && j < m; ++j)
+    if (!yy[j] || !ssp::aligned16(yy[j]))
+      return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null or misaligned destination");
+  if (ssp::exact_mode(ctx, n)) {
+    std::vector<double*> w(static_cast<size_t>(k), nullptr);
+    int status = SSP_OK;
+    for (int i = 0; status == SSP_OK && i < k; ++i) {
+      status = ssp_alloc(ctx, n, &w[size_t(i)]);
+      if (status == SSP_OK) status = ssp_mx_copy(ctx, w[size_t(i)], SSP_F64, xx[i], SSP_F32, 1.0, n);
+    }
+    if (status == SSP_OK)
+      status = solution_f64(ctx, palphas, ptr, idx, val, kp, alphas, w.data(), nullptr, k, yy, ys, m, n, offset, rmw, what);
+    for (double* b : w)
+      if (b) (void)ssp_free(ctx, b);  // stream-ordered reuse: the launches above read them first
+    return status;
+  }
+  return solution_impl(ctx, palphas, ptr, idx, val, kp, alphas, xx, static_cast<const double*>(nullptr), k, yy, ys, m,
+                       n, offset, rmw, what,
+                       [&] { return ssp::q32_dense_pass(ctx, alphas, xx, k, yy, ys, m, n, !rmw); });
 }
 }  // namespace
 
@@ -729,22 +774,36 @@ extern "C" {
 int ssp_construct_solution(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const size_t* idx,
                            const double* val, int kp, const double* alphas, const double* const* xx, int k,
                            double* const* yy, int m, size_t n, size_t offset) {
-  return solution_impl(ctx, palphas, ptr, idx, val, kp, alphas, xx, nullptr, k, yy, nullptr, m, n, offset, false,
-                       "ssp_construct_solution");
+  return solution_f64(ctx, palphas, ptr, idx, val, kp, alphas, xx, nullptr, k, yy, nullptr, m, n, offset, false,
+                      "ssp_construct_solution");
 }
 
 int ssp_construct_solution_scaled(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const size_t* idx,
                                   const double* val, int kp, const double* alphas, const double* const* xx,
                                   const double* xs, int k, double* const* yy, int m, size_t n, size_t offset) {
-  return solution_impl(ctx, palphas, ptr, idx, val, kp, alphas, xx, xs, k, yy, nullptr, m, n, offset, false,
-                       "ssp_construct_solution_scaled");
+  return solution_f64(ctx, palphas, ptr, idx, val, kp, alphas, xx, xs, k, yy, nullptr, m, n, offset, false,
+                      "ssp_construct_solution_scaled");
 }
 
 int ssp_block_update(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const size_t* idx, const double* val,
                      int kp, const double* alphas, const double* const* xx, const double* xs, int k, double* const* yy,
                      const double* ys, int m, size_t n, size_t offset) {
-  return solution_impl(ctx, palphas, ptr, idx, val, kp, alphas, xx, xs, k, yy, ys, m, n, offset, true,
-                       "ssp_block_update");
+  return solution_f64(ctx, palphas, ptr, idx, val, kp, alphas, xx, xs, k, yy, ys, m, n, offset, true,
+                      "ssp_block_update");
+}
+
+int ssp_q32_construct_solution(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const size_t* idx,
+                               const double* val, int kp, const double* alphas, const float* const* xx, int k,
+                               double* const* yy, int m, size_t n, size_t offset) {
+  return solution_f32(ctx, palphas, ptr, idx, val, kp, alphas, xx, k, yy, nullptr, m, n, offset, false,
+                      "ssp_q32_construct_solution");
+}
+
+int ssp_q32_block_update(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const size_t* idx, const double* val,
+                         int kp, const double* alphas, const float* const* xx, int k, double* const* yy,
+                         const double* ys, int m, size_t n, size_t offset) {
+  return solution_f32(ctx, palphas, ptr, idx, val, kp, alphas, xx, k, yy, ys, m, n, offset, true,
+                      "ssp_q32_block_update");
 }
 
 }  // extern "C"

@@ -478,6 +478,11 @@ int exact_inner(ssp_ctx* ctx, const double* const* xx, const double* xs, int m, 
 int exact_outer(ssp_ctx* ctx, const double* alphas, const double* const* xx, const double* xs, int k,
                 double* const* yy, const double* ys, int m, size_t n, bool set);
 
+// kernels_mixed.hip: the dense pass of the ssp_q32_* updates outside exact mode (f32 sources read as
+// stored, f64 destinations; ys: the destinations' deferred scales of the read-modify-write form, or null).
+int q32_dense_pass(ssp_ctx* ctx, const double* alphas, const float* const* xx, int k, double* const* yy,
+                   const double* ys, int m, size_t n, bool set);
+
 // kernels_stream.hip
 // pub (one rank: fold_begin's tail with a host buffer): the sums go straight to the coherent host result
 // buffer at the same offsets as in `out`, and the call's last pass (last = true) raises its flag;

@@ -386,6 +386,14 @@ bool fused_overlap_rows(H&, const RefL&, const std::vector<RefC>&, M&) {
   return false;
 }
 
+// The same hook for solvers whose R and Q vectors live in containers of their own: `rq` is the R x Q
+// handler, the columns are `rcols` concatenated, then `qcols` concatenated, and out has them in that
+// order; returns false when the handler has no such form.  Found by argument-dependent lookup.
+template <class H, class RefR, class RefQ, class M>
+bool fused_overlap_rows_mixed(H&, const RefR&, const std::vector<RefR>&, const std::vector<RefQ>&, M&) {
+  return false;
+}
+
 // Hook for an overlap whose result is needed only after more work has been queued (the subspace
 // update's S(R, P) / H(P, R) rows, queued ahead of the dense rows so that one wait covers both):
 // returns a function delivering gemm_inner(rows, cols), or an empty function when the handler has no

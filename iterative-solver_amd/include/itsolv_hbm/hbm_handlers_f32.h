@@ -8,7 +8,7 @@
 //   qq       ArrayHandlerMx<VecF32, VecF32>  construct_dspace, the Q space's own algebra
 //   qp       ArrayHandlerMxSparse            VecF32 x P through a widened scratch Vec (not hot)
 //   pp       ArrayHandlerSparse
-// Every operation is one ssp_mx_* call (include/subspace_hip.h "mixed precision"): f32 operands are
+// Every handler operation is one ssp_mx_* call (include/subspace_hip.h "mixed precision"): f32 operands are
 // widened as they are loaded, the arithmetic is the f64 entry point's, an f32 destination is rounded
 // once as it is stored.  A Vec operand's deferred scale rides along as the call's xs / ys.
 //
@@ -277,9 +277,23 @@ class ArrayHandlerMxSparse : public array::ArrayHandler<VecF32, SparseP> {
   itsolv::subspace::Matrix<double> gemm_inner(const itsolv::CVecRef<VecF32>& xx,
                                               const itsolv::CVecRef<SparseP>& yy) override {
     m_counter->gemm_inner++;
-    std::vector<Vec> w;
-    for (auto& x : xx) w.push_back(mx::widened(x.get()));
-    return m_f64.gemm_inner(itsolv::CVecRef<Vec>(w.begin(), w.end()), yy);
+    // one row at a time through one reused scratch Vec: a sparse inner product is a per-row sum over the
+    // P entries, so the rows are independent and only one widened vector is alive at any time.  The
+    // price is one sparse inner product, with its host round trip, per row instead of one for all rows:
+    // this handler is not on the hot path (Q x P overlaps of the few new Q vectors).
+    itsolv::subspace::Matrix<double> out({xx.size(), yy.size()});
+    if (xx.empty() || yy.empty()) return out;
+    const VecF32& x0 = xx.front().get();
+    Vec w(x0.device(), x0.size());
+    for (size_t i = 0; i < xx.size(); ++i) {
+      const VecF32& x = xx[i].get();
+      if (!x.compatible(x0)) error("ArrayHandlerMxSparse::gemm_inner() arrays have different distributions");
+      check_status<array::util::ArrayHandlerError>(
+          ssp_mx_copy(x.ctx(), w.data_wo(), SSP_F64, x.data(), SSP_F32, 1.0, x.local_size()), "ssp_mx_copy");
+      const auto row = m_f64.gemm_inner(itsolv::CVecRef<Vec>{std::cref(w)}, yy);
+      for (size_t j = 0; j < yy.size(); ++j) out(i, j) = row(0, j);
+    }
+    return out;
   }
   std::map<size_t, double> select_max_dot(size_t n, const VecF32& x, const SparseP& y) override {
     return m_f64.select_max_dot(n, mx::widened(x), y);
@@ -305,27 +319,98 @@ inline std::shared_ptr<itsolv::ArrayHandlers<Vec, VecF32, SparseP>> make_handler
       .build_shared();
 }
 
-// construct_solution over an f32 Q space (array::fused_construct_solution hook): the Q and D sources --
-// every stream of the pass but the destinations -- are read as f32 by one write-only gemm_outer (no zero
-// fill, no read of the destinations; each element the f64 sum of its sources in order), then the few
-// entries of the sparse P vectors are added.  The reference adds the P terms first: on the P indices the
-// same terms are summed in another order, elsewhere the result is the reference sequence's bit for bit.
-inline bool fused_construct_solution(array::ArrayHandler<Vec, SparseP>& hp, const itsolv::subspace::Matrix<double>& cp,
+// construct_solution over an f32 Q space (array::fused_construct_solution hook): one
+// ssp_q32_construct_solution.  The Q and D sources -- every stream of the pass but the destinations --
+// are read as f32 by a write-only pass (no zero fill, no read of the destinations), and the indices the
+// sparse P vectors touch are recomputed P first: the reference sequence on the widened sources, bit for
+// bit, as the f64 path's ssp_construct_solution_scaled.
+inline bool fused_construct_solution(array::ArrayHandler<Vec, SparseP>&, const itsolv::subspace::Matrix<double>& cp,
                                      const itsolv::CVecRef<SparseP>& pp, const itsolv::subspace::Matrix<double>& cqd,
                                      const itsolv::CVecRef<VecF32>& qd, const itsolv::VecRef<Vec>& yy) {
-  if (yy.empty() || qd.empty() || cqd.cols() > yy.size() || cqd.rows() != qd.size() || cp.rows() != pp.size() ||
+  if (yy.empty() || cqd.cols() > yy.size() || cqd.rows() != qd.size() || cp.rows() != pp.size() ||
       (!pp.empty() && cp.cols() != cqd.cols()))
     return false;
-  const itsolv::VecRef<Vec> dest(yy.begin(), yy.begin() + long(cqd.cols()));
-  std::vector<const void*> xp;
+  std::vector<size_t> ptr{0}, idx;
+  std::vector<double> val;
+  if (!pp.empty()) detail::pack(pp, ptr, idx, val);
+  std::vector<const float*> xp;
   for (auto& q : qd) xp.push_back(q.get().data());
-  std::vector<void*> yp;
-  for (auto& y : dest) yp.push_back(y.get().data_wo());
+  auto yp = detail::wo_ptrs(itsolv::VecRef<Vec>(yy.begin(), yy.begin() + long(cqd.cols())));
   const auto& y0 = yy.front().get();
-  check(ssp_mx_gemm_outer(y0.ctx(), cqd.data().data(), xp.data(), SSP_F32, nullptr, int(qd.size()), yp.data(), SSP_F64,
-                          int(cqd.cols()), y0.local_size(), 1),
-        "ssp_mx_gemm_outer");
-  if (!pp.empty()) hp.gemm_outer(cp, pp, dest);
+  check(ssp_q32_construct_solution(y0.ctx(), cp.data().data(), ptr.data(), idx.data(), val.data(), int(pp.size()),
+                                   cqd.data().data(), xp.data(), int(qd.size()), yp.data(), int(cqd.cols()),
+                                   y0.local_size(), y0.offset()),
+        "ssp_q32_construct_solution");
+  return true;
+}
+
+// The block Gram-Schmidt update over an f32 Q space (array::fused_block_update hook, rspace.h
+// block_gram_schmidt): one ssp_q32_block_update -- bit-identical to gemm_outer(P) then gemm_outer(Q, D)
+// on widened sources, and the destinations' deferred normalisation scale is applied as they are read
+// instead of costing a pass of its own.
+inline bool fused_block_update(array::ArrayHandler<Vec, SparseP>&, const itsolv::subspace::Matrix<double>& cp,
+                               const itsolv::CVecRef<SparseP>& pp, const itsolv::subspace::Matrix<double>& cqd,
+                               const itsolv::CVecRef<VecF32>& qd, const itsolv::VecRef<Vec>& yy) {
+  const size_t m = yy.size();
+  if (m == 0 || cqd.rows() != qd.size() || cp.rows() != pp.size() || (!qd.empty() && cqd.cols() != m) ||
+      (!pp.empty() && cp.cols() != m))
+    return false;
+  std::vector<size_t> ptr{0}, idx;
+  std::vector<double> val;
+  if (!pp.empty()) detail::pack(pp, ptr, idx, val);
+  std::vector<const float*> xp;
+  for (auto& q : qd) xp.push_back(q.get().data());
+  std::vector<double> ys;
+  auto yp = detail::rw_deferred_ptrs(yy, ys);
+  const auto& y0 = yy.front().get();
+  check(ssp_q32_block_update(y0.ctx(), cp.data().data(), ptr.data(), idx.data(), val.data(), int(pp.size()),
+                             cqd.data().data(), xp.data(), int(qd.size()), yp.data(), ys.data(), int(m),
+                             y0.local_size(), y0.offset()),
+        "ssp_q32_block_update");
+  detail::scales_applied(yy);
+  return true;
+}
+
+// The new rows of the subspace matrices over f64 and f32 columns as one ssp_q32_gemm_inner_cols
+// (array::fused_overlap_rows_mixed hook; subspace.h new_qspace_data, rspace.h append_overlap_with_r): the
+// rows are read once per launch of 64 columns whatever the columns' storage, where the block-by-block
+// overlaps are one call, one host round trip and one read of the rows per block.  From fused_min_size(),
+// as the other fused solver passes.
+inline bool fused_overlap_rows_mixed(array::ArrayHandler<Vec, VecF32>&, const itsolv::CVecRef<Vec>& rows,
+                                     const std::vector<itsolv::CVecRef<Vec>>& rcols,
+                                     const std::vector<itsolv::CVecRef<VecF32>>& qcols,
+                                     itsolv::subspace::Matrix<double>& out) {
+  if (rows.empty() || rows.front().get().size() < fused_min_size()) return false;
+  const Vec& x0 = rows.front().get();
+  auto same = [&](size_t size, size_t offset, size_t local) {
+    if (size != x0.size() || offset != x0.offset() || local != x0.local_size())
+      throw array::util::ArrayHandlerError{"fused_overlap_rows_mixed: arrays have different distributions"};
+  };
+  std::vector<double> xs, ys;
+  auto xp = detail::deferred_ptrs(rows, xs);
+  std::vector<const void*> yp;
+  std::vector<ssp_dtype> ty;
+  for (const auto& c : rcols)
+    for (auto& v : c) {
+      same(v.get().size(), v.get().offset(), v.get().local_size());
+      yp.push_back(v.get().data_deferred());
+      ys.push_back(v.get().scale());
+      ty.push_back(SSP_F64);
+    }
+  for (const auto& c : qcols)
+    for (auto& v : c) {
+      same(v.get().size(), v.get().offset(), v.get().local_size());
+      yp.push_back(v.get().data());
+      ys.push_back(1.0);
+      ty.push_back(SSP_F32);
+    }
+  if (yp.empty()) return false;
+  for (auto& r : rows) same(r.get().size(), r.get().offset(), r.get().local_size());
+  std::vector<double> buf(rows.size() * yp.size(), 0.0);
+  check(ssp_q32_gemm_inner_cols(x0.ctx(), xp.data(), xs.data(), int(rows.size()), yp.data(), ty.data(), ys.data(),
+                                int(yp.size()), x0.local_size(), buf.data()),
+        "ssp_q32_gemm_inner_cols");
+  out = itsolv::subspace::Matrix<double>(std::move(buf), {rows.size(), yp.size()});
   return true;
 }
 

@@ -156,6 +156,20 @@ Matrix<double> append_overlap_with_r(const Matrix<double>& overlap, const CVecRe
         for (size_t j = 0; j < nD; ++j) ov(oN + i, oD + j) = g(i, nN + nQ + j);
       }
     }
+  } else {
+    // R and Q in containers of their own: the same columns through the R x Q handler's batched form
+    // (array::fused_overlap_rows_mixed)
+    Matrix<double> g;
+    using array::fused_overlap_rows_mixed;
+    if (nN > 0 && fused_overlap_rows_mixed(h.rq(), params, std::vector<CVecRef<R>>{params},
+                                           std::vector<CVecRef<Q>>{qp, dp}, g)) {
+      fused = true;
+      for (size_t i = 0; i < nN; ++i) {
+        for (size_t j = 0; j <= i; ++j) ov(oN + i, oN + j) = ov(oN + j, oN + i) = g(i, j);
+        for (size_t j = 0; j < nQ; ++j) ov(oN + i, oQ + j) = g(i, nN + j);
+        for (size_t j = 0; j < nD; ++j) ov(oN + i, oD + j) = g(i, nN + nQ + j);
+      }
+    }
   }
   if (!fused) {
     ov.slice({oN, oN}, {nX, nX}) = subspace::util::overlap(params, h.rr());

@@ -363,6 +363,43 @@ class XSpace {
         p_rows = queued_overlap(h.rp(), both, pp);
       }
     }
+    // The batched rows g (columns [params, actions, Q params, Q actions, D params, D actions, rhs]) into
+    // the new data; for action . action (DIIS) the S rows g from the parameters ([params, Q params,
+    // D params, rhs]) and the H rows ga from the actions ([actions, Q actions, D actions]).
+    auto take_rows = [&](const Matrix<double>& g) {
+      const size_t cA = nn, cQ = 2 * nn, cQA = cQ + d.nQ, cD = cQA + d.nQ, cDA = cD + d.nD, cR = cDA + d.nD;
+      for (size_t i = 0; i < nn; ++i) {
+        for (size_t j = 0; j <= i; ++j) qq[EqnData::S](i, j) = qq[EqnData::S](j, i) = g(i, j);
+        for (size_t j = 0; j < nn; ++j) qq[EqnData::H](i, j) = g(i, cA + j);
+        for (size_t j = 0; j < d.nQ; ++j) {
+          qx[EqnData::S](i, d.oQ + j) = g(i, cQ + j);
+          qx[EqnData::H](i, d.oQ + j) = g(i, cQA + j);
+        }
+        for (size_t j = 0; j < d.nD; ++j) {
+          qx[EqnData::S](i, d.oD + j) = g(i, cD + j);
+          qx[EqnData::H](i, d.oD + j) = g(i, cDA + j);
+        }
+        for (size_t j = 0; j < m_rhs.size(); ++j) qq[EqnData::rhs](i, j) = g(i, cR + j);
+      }
+    };
+    auto take_rows_ada = [&](const Matrix<double>& g, const Matrix<double>& ga) {
+      const size_t cQ = nn, cD = cQ + d.nQ, cR = cD + d.nD;
+      for (size_t i = 0; i < nn; ++i) {
+        for (size_t j = 0; j <= i; ++j) {
+          qq[EqnData::S](i, j) = qq[EqnData::S](j, i) = g(i, j);
+          qq[EqnData::H](i, j) = qq[EqnData::H](j, i) = ga(i, j);
+        }
+        for (size_t j = 0; j < d.nQ; ++j) {
+          qx[EqnData::S](i, d.oQ + j) = g(i, cQ + j);
+          qx[EqnData::H](i, d.oQ + j) = ga(i, nn + j);
+        }
+        for (size_t j = 0; j < d.nD; ++j) {
+          qx[EqnData::S](i, d.oD + j) = g(i, cD + j);
+          qx[EqnData::H](i, d.oD + j) = ga(i, nn + d.nQ + j);
+        }
+        for (size_t j = 0; j < m_rhs.size(); ++j) qq[EqnData::rhs](i, j) = g(i, cR + j);
+      }
+    };
     if constexpr (std::is_same_v<R, Q>) {
       // every block whose rows are the new parameters, as one batched overlap where the handler has
       // it: columns [params, actions, Q params, Q actions, D params, D actions, rhs]
@@ -371,20 +408,7 @@ class XSpace {
       if (!m_action_dot_action && nn > 0 &&
           fused_overlap_rows(h.rr(), params, std::vector<CVecRef<R>>{params, actions, qp, qa, dp, da, rhs()}, g)) {
         fused = true;
-        const size_t cA = nn, cQ = 2 * nn, cQA = cQ + d.nQ, cD = cQA + d.nQ, cDA = cD + d.nD, cR = cDA + d.nD;
-        for (size_t i = 0; i < nn; ++i) {
-          for (size_t j = 0; j <= i; ++j) qq[EqnData::S](i, j) = qq[EqnData::S](j, i) = g(i, j);
-          for (size_t j = 0; j < nn; ++j) qq[EqnData::H](i, j) = g(i, cA + j);
-          for (size_t j = 0; j < d.nQ; ++j) {
-            qx[EqnData::S](i, d.oQ + j) = g(i, cQ + j);
-            qx[EqnData::H](i, d.oQ + j) = g(i, cQA + j);
-          }
-          for (size_t j = 0; j < d.nD; ++j) {
-            qx[EqnData::S](i, d.oD + j) = g(i, cD + j);
-            qx[EqnData::H](i, d.oD + j) = g(i, cDA + j);
-          }
-          for (size_t j = 0; j < m_rhs.size(); ++j) qq[EqnData::rhs](i, j) = g(i, cR + j);
-        }
+        take_rows(g);
       }
       // action . action (DIIS): the S rows from the parameters, the H rows from the actions -- two
       // batched overlaps: [params, Q params, D params, rhs] and [actions, Q actions, D actions]
@@ -393,22 +417,27 @@ class XSpace {
           fused_overlap_rows(h.rr(), params, std::vector<CVecRef<R>>{params, qp, dp, rhs()}, g) &&
           fused_overlap_rows(h.rr(), actions, std::vector<CVecRef<R>>{actions, qa, da}, ga)) {
         fused = true;
-        const size_t cQ = nn, cD = cQ + d.nQ, cR = cD + d.nD;
-        for (size_t i = 0; i < nn; ++i) {
-          for (size_t j = 0; j <= i; ++j) {
-            qq[EqnData::S](i, j) = qq[EqnData::S](j, i) = g(i, j);
-            qq[EqnData::H](i, j) = qq[EqnData::H](j, i) = ga(i, j);
-          }
-          for (size_t j = 0; j < d.nQ; ++j) {
-            qx[EqnData::S](i, d.oQ + j) = g(i, cQ + j);
-            qx[EqnData::H](i, d.oQ + j) = ga(i, nn + j);
-          }
-          for (size_t j = 0; j < d.nD; ++j) {
-            qx[EqnData::S](i, d.oD + j) = g(i, cD + j);
-            qx[EqnData::H](i, d.oD + j) = ga(i, nn + d.nQ + j);
-          }
-          for (size_t j = 0; j < m_rhs.size(); ++j) qq[EqnData::rhs](i, j) = g(i, cR + j);
-        }
+        take_rows_ada(g, ga);
+      }
+    } else {
+      // R and Q in containers of their own: the same column sets, the R columns and the Q columns as
+      // two lists, where the R x Q handler has the batched form (array::fused_overlap_rows_mixed)
+      Matrix<double> g;
+      using array::fused_overlap_rows_mixed;
+      if (!m_action_dot_action && nn > 0 &&
+          fused_overlap_rows_mixed(h.rq(), params, std::vector<CVecRef<R>>{params, actions},
+                                   std::vector<CVecRef<Q>>{qp, qa, dp, da, rhs()}, g)) {
+        fused = true;
+        take_rows(g);
+      }
+      Matrix<double> ga;
+      if (m_action_dot_action && nn > 0 &&
+          fused_overlap_rows_mixed(h.rq(), params, std::vector<CVecRef<R>>{params},
+                                   std::vector<CVecRef<Q>>{qp, dp, rhs()}, g) &&
+          fused_overlap_rows_mixed(h.rq(), actions, std::vector<CVecRef<R>>{actions}, std::vector<CVecRef<Q>>{qa, da},
+                                   ga)) {
+        fused = true;
+        take_rows_ada(g, ga);
       }
     }
     if (!fused) {

@@ -52,12 +52,17 @@ EXPORTS = [
     # vectors stored in f32, arithmetic in f64
     "ssp_alloc_f32", "ssp_free_f32", "ssp_upload_f32", "ssp_download_f32", "ssp_fill_f32", "ssp_scal_f32",
     "ssp_mx_copy", "ssp_mx_axpy", "ssp_mx_dot", "ssp_mx_gemm_inner", "ssp_mx_gemm_outer",
+    # fused solver passes over an f32 Q space beside f64 R vectors
+    "ssp_q32_gemm_inner_cols", "ssp_q32_construct_solution", "ssp_q32_block_update",
 ]
 
 # The mixed-precision entry points are optional in a loaded library: the CPU emulation of the f64 C ABI
 # (loaded through these bindings by patching LIB_PATH) does not have them, and a call then raises
 # SspError(SSP_ERR_UNSUPPORTED).
 OPTIONAL = frozenset(n for n in EXPORTS if n.endswith("_f32") or n.startswith("ssp_mx_"))
+# The fused passes over an f32 Q space are tolerated in the same way (absent from the emulation, a call
+# raises SspError(SSP_ERR_UNSUPPORTED)); they are a set of their own: OPTIONAL stays the storage layer.
+OPTIONAL_Q32 = frozenset(n for n in EXPORTS if n.startswith("ssp_q32_"))
 SSP_F64, SSP_F32 = 0, 1
 
 
@@ -183,9 +188,12 @@ def _declare(lib):
         "ssp_mx_dot": (I, [P, P, I, P, I, Z, PD]),
         "ssp_mx_gemm_inner": (I, [P, P, I, PD, I, P, I, PD, I, Z, PD]),
         "ssp_mx_gemm_outer": (I, [P, PD, P, I, PD, I, P, I, I, Z, I]),
+        "ssp_q32_gemm_inner_cols": (I, [P, P, PD, I, P, C.POINTER(I), PD, I, Z, PD]),
+        "ssp_q32_construct_solution": (I, [P, PD, PZ, PZ, PD, I, PD, P, I, P, I, Z, Z]),
+        "ssp_q32_block_update": (I, [P, PD, PZ, PZ, PD, I, PD, P, I, P, PD, I, Z, Z]),
     }
     for name, (res, args) in sig.items():
-        if name in OPTIONAL and not hasattr(lib, name):
+        if (name in OPTIONAL or name in OPTIONAL_Q32) and not hasattr(lib, name):
             continue
         f = getattr(lib, name)
         f.restype = res
@@ -453,7 +461,8 @@ class Context:
 
     # -- memory -----------------------------------------------------------------------------
     def _mx(self, name: str):
-        """A mixed-precision entry point of the loaded library (OPTIONAL: absent from the emulation)."""
+        """A mixed-precision entry point of the loaded library (OPTIONAL / OPTIONAL_Q32: absent from the
+        emulation)."""
         f = getattr(self.lib, name, None)
         if f is None:
             raise SspError(7, f"{name}: the loaded library has no mixed-precision entry points")
@@ -811,6 +820,50 @@ class Context:
         n = yy[0].n if yy else 0
         _check(f(self.handle, _dptr(alphas), _ptrs(xx), _same_dtype(xx), _dptr(a), len(xx), _ptrs(yy),
                  _same_dtype(yy), len(yy), n, int(bool(set))))
+
+    # -- fused solver passes over an f32 Q space (include/subspace_hip.h ssp_q32_*) -----------------
+    def q32_gemm_inner_cols(self, rows, cols, xs=None, ys=None) -> np.ndarray:
+        """<xs[i] rows[i], ys[j] cols[j]>: rows float64, each column float64 or float32, in any order."""
+        f = self._mx("ssp_q32_gemm_inner_cols")
+        if any(_code(v) != SSP_F64 for v in rows):
+            raise TypeError("q32_gemm_inner_cols: the rows are float64 vectors")
+        m, k = len(rows), len(cols)
+        out = np.zeros((m, k))
+        a, b = self._scales(xs, m), self._scales(ys, k)
+        ty = (C.c_int * max(1, k))(*[_code(v) for v in cols])
+        n = rows[0].n if m else (cols[0].n if k else 0)
+        _check(f(self.handle, _ptrs(rows), _dptr(a), m, _ptrs(cols), ty, _dptr(b), k, n, _dptr(out)))
+        return out
+
+    @staticmethod
+    def _f32_sources(xx, what):
+        if any(_code(v) != SSP_F32 for v in xx):
+            raise TypeError(f"{what}: the dense sources are float32 vectors")
+
+    def q32_construct_solution(self, palphas, ps, alphas, xx, yy, offset: int = 0):
+        """construct_solution with float32 dense sources xx and float64 destinations yy."""
+        f = self._mx("ssp_q32_construct_solution")
+        self._f32_sources(xx, "q32_construct_solution")
+        m = len(yy)
+        pa = np.ascontiguousarray(palphas, dtype=np.float64).reshape(len(ps), m)
+        al = np.ascontiguousarray(alphas, dtype=np.float64).reshape(len(xx), m)
+        ptr, idx, val = self._pack_sparse(ps)
+        n = yy[0].n if m else 0
+        _check(f(self.handle, _dptr(pa), _zptr(ptr), _zptr(idx), _dptr(val), len(ps), _dptr(al), _ptrs(xx), len(xx),
+                 _ptrs(yy), m, n, offset))
+
+    def q32_block_update(self, palphas, ps, alphas, xx, yy, ys=None, offset: int = 0):
+        """yy[j] = ys[j] yy[j] + sum_i palphas[i, j] p_i + sum_s alphas[s, j] xx[s], xx float32."""
+        f = self._mx("ssp_q32_block_update")
+        self._f32_sources(xx, "q32_block_update")
+        m = len(yy)
+        pa = np.ascontiguousarray(palphas, dtype=np.float64).reshape(len(ps), m)
+        al = np.ascontiguousarray(alphas, dtype=np.float64).reshape(len(xx), m)
+        b = self._scales(ys, m)
+        ptr, idx, val = self._pack_sparse(ps)
+        n = yy[0].n if m else 0
+        _check(f(self.handle, _dptr(pa), _zptr(ptr), _zptr(idx), _dptr(val), len(ps), _dptr(al), _ptrs(xx), len(xx),
+                 _ptrs(yy), _dptr(b), m, n, offset))
 
     # -- deferred scal (include/subspace_hip.h *_scaled): each operand with a pending scale ---------
     @staticmethod

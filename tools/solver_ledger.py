@@ -4,7 +4,7 @@ ledger enabled and report, per handler operation, calls, kernel time, algorithmi
 plus the solve's wall time.  Complements bench.py (a fixed subspace-update step) with the op mix
 of real Davidson / DIIS iterations.
 
-usage: python tools/solver_ledger.py [--configs C2,C2-mgs,C3,C3-mgs,C5,C4-shard] [--out profiles/r1/solver_ledger.json]
+usage: python tools/solver_ledger.py [--configs C2,C2-mgs,C3,C3-mgs,C5,C4-shard] [--q32] [--out profiles/r1/solver_ledger.json]
 """
 import argparse
 import json
@@ -39,7 +39,10 @@ CONFIGS = {
     "C4-shard": ("davidson", 12_500_000, dict(rho=0.1, rank=8, seed=1, nroots=8, max_p=16, max_size_qspace=48,
                                               reset_D=8, convergence_threshold=1e-8)),
 }
-REDUCING = ("dot", "gemm_inner", "axpy_inner", "scal_inner", "axpy_norm", "axpy_gram", "axpy_pairs_norm", "select", "gemm_inner_sparse")
+REDUCING = ("dot", "gemm_inner", "axpy_inner", "scal_inner", "axpy_norm", "axpy_gram", "axpy_pairs_norm", "select", "gemm_inner_sparse",
+            # a Q space stored in f32 (--q32)
+            "dot_f32", "gemm_inner_f32", "gemm_inner_cols")
+Q32 = False  # --q32: the Davidson configs with the Q space stored in f32
 
 
 def run(ctx, name, repeat=2):
@@ -63,7 +66,7 @@ def run_once(ctx, name):
     ctx.ledger_enable(True)
     t0 = time.perf_counter()
     if solver == "davidson":
-        r = ih.davidson_synthetic(ctx, n, rho, rank, seed, n_local=0, **kw)
+        r = ih.davidson_synthetic(ctx, n, rho, rank, seed, n_local=0, q32=Q32, **kw)
     else:
         r = ih.diis_synthetic(ctx, n, rho, rank, seed, n_local=0, **kw)
     wall = time.perf_counter() - t0
@@ -75,7 +78,7 @@ def run_once(ctx, name):
                 "GBs": round(v["bytes"] / (v["ms"] / 1e3) / 1e9, 1) if v["ms"] > 0 else None,
                 "share_of_kernel_time": round(v["ms"] / ms, 4) if ms else None}
            for op, v in sorted(led.items(), key=lambda kv: -kv[1]["ms"])}
-    out = {"config": name, "solver": solver, "n": n, "options": CONFIGS[name][2], "converged": r["converged"],
+    out = {"config": name + ("-q32" if Q32 and solver == "davidson" else ""), "solver": solver, "n": n, "options": CONFIGS[name][2], "converged": r["converged"],
            "iterations": r["iterations"], "wall_s": round(wall, 3), "kernel_ms": round(ms, 3),
            "algorithmic_GB": round(nb / 1e9, 3), "kernel_GBs": round(nb / (ms / 1e3) / 1e9, 1) if ms else None,
            "wall_GBs": round(nb / wall / 1e9, 1), "ops": ops,
@@ -96,7 +99,10 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "solver_ledger.json"))
     ap.add_argument("--rccl", action="store_true", help="attach a one-rank RCCL communicator (multi-rank path)")
     ap.add_argument("--p2p", action="store_true", help="attach a one-rank peer-memory communicator (multi-rank path)")
+    ap.add_argument("--q32", action="store_true", help="Davidson configs with the Q space stored in f32")
     a = ap.parse_args()
+    global Q32
+    Q32 = a.q32
     ctx = sh.Context(0)
     if a.rccl:
         ctx.attach_comm(1, 0, sh.Context.unique_id())
