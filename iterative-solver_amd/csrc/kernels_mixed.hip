@@ -10,12 +10,20 @@
 //   gemm_outer  bytes = N (sx k + (1 or 2) sy m)      gemm_inner  bytes = N (sx m + sy k)
 // with sx, sy the storage sizes: 48 f32 sources into 8 f64 destinations move 320 N bytes where the f64
 // kernel moves 512 N.
+//
+// Kernels.  k_mx_copy, k_mx_axpy, k_mx_scal, k_mx_dot: one per-element operation each, over map_quads;
+// k_mx_fill; k_mx_outer<TX, TY, M, SET> (gemm_outer, launched chunk by chunk from outer_chunks, also the
+// dense pass of the ssp_q32_* updates); k_mx_inner<TX, CP, MG, NG> (gemm_inner: the one MFMA tile kernel,
+// CP the columns' storage -- float, double, or ByGroup for ssp_q32_gemm_inner_cols).  with_pair maps the
+// storage pair of a call to the kernel's types.
 #include <algorithm>
 #include <cstddef>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
+#include "mfma_tile.h"
 #include "mx_cols_plan.h"
 #include "ssp_internal.h"
 
@@ -102,86 +110,76 @@ __device__ __forceinline__ void for_quads(size_t n, FW&& fw, F&& f, FE&& fe) {
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) fe(4 * n4 + threadIdx.x);
 }
 
+// The lane's U quads pos[u] of one vector, as loaded.
+template <typename T, int U>
+struct Win {
+  Raw<T> q[U];
+};
+template <bool NT, typename T, int U>
+__device__ __forceinline__ Win<T, U> ldwin(const T* p, const size_t (&pos)[U]) {
+  Win<T, U> w;
+#pragma unroll
+  for (int u = 0; u < U; ++u) w.q[u] = ldq<NT>(p + 4 * pos[u]);
+  return w;
+}
+
 unsigned quad_grid(const ssp_ctx* ctx, size_t n, int u, unsigned per_cu) {
   return ssp::stream_grid(ctx, ((n >> 2) / (64 * size_t(u)) + 1) * 64, 1, per_cu);
 }
 
 constexpr int kMxU = 4;  // 4 KiB of an f32 vector, 8 KiB of an f64 one, per wave visit
 
+// One operation over the lane's U quads p0 + 64 u of every operand, written once:
+// f(e, in0, in1, ...) gets element e of the quad of every input, widened, and returns the f64 value stored
+// (rounded) to `out`; with out = nullptr nothing is stored and f only accumulates.  Every load of a visit
+// is issued, operand by operand, before the first f, then come the stores.  NT: nontemporal accesses.
+template <int U, bool NT, typename O, typename F, typename... TI>
+__device__ __forceinline__ void map_quads_at(size_t p0, O out, F& f, const TI*... in) {
+  size_t pos[U];  // formed once for every operand: each vector's addresses then share them, as written by hand
+#pragma unroll
+  for (int u = 0; u < U; ++u) pos[u] = p0 + 64 * u;
+  const auto apply = [&](const auto&... v) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      double w[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if constexpr (std::is_null_pointer_v<O>) f(e, v.q[u].get(e)...);
+        else w[e] = f(e, v.q[u].get(e)...);
+      if constexpr (!std::is_null_pointer_v<O>) stq<NT>(out + 4 * pos[u], w);
+    }
+  };
+  apply(ldwin<NT>(in, pos)...);
+}
+
+// for_quads<kMxU> with the one per-element operation f: the window form (nontemporal), the single quad
+// (plain accesses) and the n mod 4 last elements, which f sees as element 0 of a quad.
+template <typename O, typename F, typename... TI>
+__device__ __forceinline__ void map_quads(size_t n, O out, F f, const TI*... in) {
+  for_quads<kMxU>(
+      n, [&](size_t p0) { map_quads_at<kMxU, true>(p0, out, f, in...); },
+      [&](size_t p) { map_quads_at<1, false>(p, out, f, in...); },
+      [&](size_t i) {
+        if constexpr (std::is_null_pointer_v<O>) f(0, double(in[i])...);
+        else out[i] = std::remove_pointer_t<O>(f(0, double(in[i])...));
+      });
+}
+
 // x = (TX)(ys * y)
 template <typename TX, typename TY>
 __global__ __launch_bounds__(kBlock) void k_mx_copy(TX* __restrict__ x, const TY* __restrict__ y, size_t n, double ys) {
-  for_quads<kMxU>(
-      n,
-      [&](size_t p0) {
-        Raw<TY> v[kMxU];
-#pragma unroll
-        for (int u = 0; u < kMxU; ++u) v[u] = ldq<true>(y + 4 * (p0 + 64 * u));
-#pragma unroll
-        for (int u = 0; u < kMxU; ++u) {
-          const double w[4] = {v[u].get(0) * ys, v[u].get(1) * ys, v[u].get(2) * ys, v[u].get(3) * ys};
-          stq<true>(x + 4 * (p0 + 64 * u), w);
-        }
-      },
-      [&](size_t p) {
-        const Raw<TY> v = ldq<false>(y + 4 * p);
-        const double w[4] = {v.get(0) * ys, v.get(1) * ys, v.get(2) * ys, v.get(3) * ys};
-        stq<false>(x + 4 * p, w);
-      },
-      [&](size_t e) { x[e] = TX(double(y[e]) * ys); });
+  map_quads(n, x, [=](int, double v) { return v * ys; }, y);
 }
 
 // y = (TY)fma(alpha, x, y): the single fma of k_axpy.
 template <typename TX, typename TY>
 __global__ __launch_bounds__(kBlock) void k_mx_axpy(const TX* __restrict__ x, TY* __restrict__ y, size_t n, double alpha) {
-  for_quads<kMxU>(
-      n,
-      [&](size_t p0) {
-        Raw<TX> xv[kMxU];
-        Raw<TY> yv[kMxU];
-#pragma unroll
-        for (int u = 0; u < kMxU; ++u) xv[u] = ldq<true>(x + 4 * (p0 + 64 * u));
-#pragma unroll
-        for (int u = 0; u < kMxU; ++u) yv[u] = ldq<true>(y + 4 * (p0 + 64 * u));
-#pragma unroll
-        for (int u = 0; u < kMxU; ++u) {
-          double w[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) w[e] = fma(alpha, xv[u].get(e), yv[u].get(e));
-          stq<true>(y + 4 * (p0 + 64 * u), w);
-        }
-      },
-      [&](size_t p) {
-        const Raw<TX> xv = ldq<false>(x + 4 * p);
-        const Raw<TY> yv = ldq<false>(y + 4 * p);
-        double w[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = fma(alpha, xv.get(e), yv.get(e));
-        stq<false>(y + 4 * p, w);
-      },
-      [&](size_t e) { y[e] = TY(fma(alpha, double(x[e]), double(y[e]))); });
+  map_quads(n, y, [=](int, double xv, double yv) { return fma(alpha, xv, yv); }, x, static_cast<const TY*>(y));
 }
 
-// x = (float)(alpha * x)
+// x = (float)(alpha * x).  Not k_mx_copy<float, float> in place: both of that kernel's pointers are restrict.
 __global__ __launch_bounds__(kBlock) void k_mx_scal(float* __restrict__ x, size_t n, double alpha) {
-  for_quads<kMxU>(
-      n,
-      [&](size_t p0) {
-        Raw<float> v[kMxU];
-#pragma unroll
-        for (int u = 0; u < kMxU; ++u) v[u] = ldq<true>(x + 4 * (p0 + 64 * u));
-#pragma unroll
-        for (int u = 0; u < kMxU; ++u) {
-          const double w[4] = {v[u].get(0) * alpha, v[u].get(1) * alpha, v[u].get(2) * alpha, v[u].get(3) * alpha};
-          stq<true>(x + 4 * (p0 + 64 * u), w);
-        }
-      },
-      [&](size_t p) {
-        const Raw<float> v = ldq<false>(x + 4 * p);
-        const double w[4] = {v.get(0) * alpha, v.get(1) * alpha, v.get(2) * alpha, v.get(3) * alpha};
-        stq<false>(x + 4 * p, w);
-      },
-      [&](size_t e) { x[e] = float(double(x[e]) * alpha); });
+  map_quads(n, x, [=](int, double v) { return v * alpha; }, static_cast<const float*>(x));
 }
 
 // x = (float)alpha: the stride shape of k_fill, one quad per lane and trip.
@@ -198,27 +196,7 @@ template <typename TX, typename TY>
 __global__ __launch_bounds__(kBlock) void k_mx_dot(const TX* __restrict__ x, const TY* __restrict__ y, size_t n,
                                                    double* __restrict__ partial, const ssp::FoldTail tail) {
   double acc[4] = {0, 0, 0, 0};
-  for_quads<kMxU>(
-      n,
-      [&](size_t p0) {
-        Raw<TX> xv[kMxU];
-        Raw<TY> yv[kMxU];
-#pragma unroll
-        for (int u = 0; u < kMxU; ++u) xv[u] = ldq<true>(x + 4 * (p0 + 64 * u));
-#pragma unroll
-        for (int u = 0; u < kMxU; ++u) yv[u] = ldq<true>(y + 4 * (p0 + 64 * u));
-#pragma unroll
-        for (int u = 0; u < kMxU; ++u)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[e] = fma(xv[u].get(e), yv[u].get(e), acc[e]);
-      },
-      [&](size_t p) {
-        const Raw<TX> xv = ldq<false>(x + 4 * p);
-        const Raw<TY> yv = ldq<false>(y + 4 * p);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] = fma(xv.get(e), yv.get(e), acc[e]);
-      },
-      [&](size_t e) { acc[0] = fma(double(x[e]), double(y[e]), acc[0]); });
+  map_quads(n, nullptr, [&](int e, double xv, double yv) { acc[e] = fma(xv, yv, acc[e]); }, x, y);
   const double s = ssp::block_sum256((acc[0] + acc[1]) + (acc[2] + acc[3]));
   if (threadIdx.x == 0) ssp::store_partial(partial + blockIdx.x, s);
   ssp::fold_tail(partial, tail);
@@ -345,71 +323,122 @@ __global__ __launch_bounds__(kBlock) void k_mx_outer(const MxOuterArgs a) {
 // ---- gemm_inner -----------------------------------------------------------------------------------
 struct MxInnerArgs {
   const void* x[ssp::kInnerRows];  // rows: MG groups of 4
-  const void* y[ssp::kInnerCols];  // columns: NG groups of 4
+  const void* y[ssp::kInnerCols];  // columns: NG groups of 4; ByGroup: the first g64 groups f64, the others f32, and
+                                   // a null one is a padding slot (never the first of its group)
   double xs[ssp::kInnerRows];
   double ys[ssp::kInnerCols];
   int m;
-  int k;
+  int k;    // ByGroup: slots, a multiple of 4
+  int g64;  // ByGroup only
   size_t n;
   double* partial;  // [gridDim.x][m][k]
 };
+static_assert(sizeof(MxInnerArgs) <= 4000, "kernel argument block too large");
 
-// The f64 MFMA tile of k_gemm_inner (v_mfma_f64_4x4x4_f64: lane l = 16k + 4b + i holds A_b[i][k] and
-// B_b[k][i], C_b[i][j] sits in lane 16i + 4b + j) over chunks of 64 elements: the 16 lanes that hold
-// one vector (same l & 3) each load the quad p = l >> 2 of the chunk -- 256 contiguous bytes of an f32
-// vector per load instruction, 512 of an f64 one per pair -- and the quad's four elements feed four
-// MFMAs (one per element; the tiles of one element are independent, so no MFMA waits for the one
-// before it).  Operands are widened and scaled (v * s, the rounding an eager scal stores) after every
-// load of the chunk is in flight.  Lanes of absent vectors read their group's first vector and feed
-// rows / columns that are never stored; whole absent groups skip their loads by a wave-uniform branch.
-template <typename TX, typename TY, int MG, int NG>
+// Storage policies of k_mx_inner: the quads of a chunk's NG column groups (with T = TX, MG row groups) as
+// loaded.  load(h, ...): the
+// nontemporal load of group h's quad, or zeros for a whole absent group (`present` is wave-uniform, so the
+// branch skips the load and no load carries an exec-mask guard); get(h, q): element q of that quad, widened;
+// elem(h, g64, p, i): element i of column p of group h, widened, for the remainder loop.
+// Every column stored as T:
+template <typename T, int NG>
+struct TileQuads {
+  Raw<T> v[NG];
+  __device__ __forceinline__ explicit TileQuads(int) {}
+  __device__ __forceinline__ void load(int h, bool present, const void* p, size_t e0) {
+    v[h] = present ? ldq<true>(static_cast<const T*>(p) + e0) : zero_quad<T>();
+  }
+  __device__ __forceinline__ double get(int h, int q) const { return v[h].get(q); }
+  __device__ __forceinline__ static double elem(int, int, const void* p, size_t i) { return double(static_cast<const T*>(p)[i]); }
+};
+
+// Either, by group (mx_cols_plan.h): group h is f64 when h < g64, a wave-uniform branch, so one launch reads
+// its rows once for the columns of both types.  Lanes of a padding slot read their group's first column;
+// what they accumulate is stored with the rest (the layout of the partials depends on the slots only) and
+// dropped by the host.
+// Registers: every group's quad has 16 bytes in lo[h] (an f32 quad, or the first half of an f64 one) and the
+// 16 more of hi[h]: any group may be f64 (H64 = NG).  A lean form (H64 = 4: the 16 f64 columns of a subspace
+// update, later groups f32 statically, the register footprint of k_mx_inner<double, float>) measured no
+// faster on the tile of 16 f64 + 48 f32 columns at N = 1.25e7 and 1e8 (profiles/r8/q32_fused.md), so it is
+// not instantiated.
+struct ByGroup {};
+template <int NG>
+struct TileQuads<ByGroup, NG> {
+  nt_float4 lo[NG];
+  nt_double2 hi[NG];
+  const int g64;
+  __device__ __forceinline__ explicit TileQuads(int g) : g64(g) {}
+  __device__ __forceinline__ void load(int h, bool present, const void* p, size_t e0) {
+    lo[h] = nt_float4{0.f, 0.f, 0.f, 0.f};
+    hi[h] = nt_double2{0., 0.};
+    if (present) {
+      if (h < g64) {
+        const Raw<double> v = ldq<true>(static_cast<const double*>(p) + e0);
+        lo[h] = __builtin_bit_cast(nt_float4, v.a);
+        hi[h] = v.b;
+      } else {
+        lo[h] = ldq<true>(static_cast<const float*>(p) + e0).a;
+      }
+    }
+  }
+  __device__ __forceinline__ double get(int h, int q) const {
+    double v = double(lo[h][q]);
+    if (h < g64) v = q < 2 ? __builtin_bit_cast(nt_double2, lo[h])[q] : hi[h][q - 2];
+    return v;
+  }
+  __device__ __forceinline__ static double elem(int h, int g64, const void* p, size_t i) {
+    return h < g64 ? static_cast<const double*>(p)[i] : double(static_cast<const float*>(p)[i]);
+  }
+};
+
+// The f64 MFMA tile of k_gemm_inner (mfma_tile.h) over chunks of 64 elements, rows stored as TX, columns by
+// the policy CP (float, double or ByGroup): the 16 lanes that hold one vector (same l & 3) each load the quad
+// p = l >> 2 of the chunk -- 256 contiguous bytes of an f32 vector per load instruction, 512 of an f64 one
+// per pair -- and the quad's four elements feed four MFMAs (one per element; the tiles of one element are
+// independent, so no MFMA waits for the one before it; each accumulator sees the elements in increasing
+// order).  Operands are widened and scaled (v * s, the rounding an eager scal stores) after every load of
+// the chunk, rows then columns, is in flight.  Whole absent groups skip their loads by a wave-uniform branch.
+template <typename TX, typename CP, int MG, int NG>
 __global__ __launch_bounds__(kBlock) void k_mx_inner(const MxInnerArgs a) {
+  static_assert(4 * MG <= ssp::kInnerRows && 4 * NG <= ssp::kInnerCols, "tile_lane reads 4 entries per group");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 3, p = lane >> 2;
-  const TX* xp[MG];
-  const TY* yp[NG];
-  double xsc[MG], ysc[NG];
-  bool xok[MG], yok[NG];
+  ssp::TileLane x[MG], y[NG];
 #pragma unroll
-  for (int g = 0; g < MG; ++g) {
-    xok[g] = 4 * g + r < a.m;
-    xp[g] = static_cast<const TX*>(xok[g] ? a.x[4 * g + r] : a.x[4 * g < a.m ? 4 * g : 0]);
-    xsc[g] = xok[g] ? a.xs[4 * g + r] : 1.0;
-  }
+  for (int g = 0; g < MG; ++g) x[g] = ssp::tile_lane(a.x, a.xs, a.m, g, r);
 #pragma unroll
-  for (int h = 0; h < NG; ++h) {
-    yok[h] = 4 * h + r < a.k;
-    yp[h] = static_cast<const TY*>(yok[h] ? a.y[4 * h + r] : a.y[4 * h < a.k ? 4 * h : 0]);
-    ysc[h] = yok[h] ? a.ys[4 * h + r] : 1.0;
-  }
+  for (int h = 0; h < NG; ++h) y[h] = ssp::tile_lane(a.y, a.ys, a.k, h, r);
   double acc[MG][NG];
 #pragma unroll
   for (int g = 0; g < MG; ++g)
 #pragma unroll
     for (int h = 0; h < NG; ++h) acc[g][h] = 0;
+  const auto mac = [&](const double (&xw)[MG], const double (&yw)[NG]) {
+#pragma unroll
+    for (int g = 0; g < MG; ++g)
+#pragma unroll
+      for (int h = 0; h < NG; ++h) acc[g][h] = __builtin_amdgcn_mfma_f64_4x4x4f64(xw[g], yw[h], acc[g][h], 0, 0, 0);
+  };
 
   const size_t gw = size_t(__builtin_amdgcn_readfirstlane(int(blockIdx.x * (kBlock / 64) + wave)));
   const size_t nw = size_t(gridDim.x) * (kBlock / 64);
   const size_t nchunks = a.n / 64;
   for (size_t ch = gw; ch < nchunks; ch += nw) {
     const size_t e0 = ch * 64 + 4 * size_t(p);
-    Raw<TX> xv[MG];
-    Raw<TY> yv[NG];
+    TileQuads<TX, MG> xv(0);
+    TileQuads<CP, NG> yv(a.g64);
 #pragma unroll
-    for (int g = 0; g < MG; ++g) xv[g] = 4 * g < a.m ? ldq<true>(xp[g] + e0) : zero_quad<TX>();
+    for (int g = 0; g < MG; ++g) xv.load(g, 4 * g < a.m, x[g].p, e0);
 #pragma unroll
-    for (int h = 0; h < NG; ++h) yv[h] = 4 * h < a.k ? ldq<true>(yp[h] + e0) : zero_quad<TY>();
+    for (int h = 0; h < NG; ++h) yv.load(h, 4 * h < a.k, y[h].p, e0);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       double xw[MG], yw[NG];
 #pragma unroll
-      for (int g = 0; g < MG; ++g) xw[g] = xv[g].get(q) * xsc[g];
+      for (int g = 0; g < MG; ++g) xw[g] = xv.get(g, q) * x[g].s;
 #pragma unroll
-      for (int h = 0; h < NG; ++h) yw[h] = yv[h].get(q) * ysc[h];
-#pragma unroll
-      for (int g = 0; g < MG; ++g)
-#pragma unroll
-        for (int h = 0; h < NG; ++h) acc[g][h] = __builtin_amdgcn_mfma_f64_4x4x4f64(xw[g], yw[h], acc[g][h], 0, 0, 0);
+      for (int h = 0; h < NG; ++h) yw[h] = yv.get(h, q) * y[h].s;
+      mac(xw, yw);
     }
   }
   // Remainder [64 nchunks, n): guarded element loads, zeros past n.
@@ -419,186 +448,13 @@ __global__ __launch_bounds__(kBlock) void k_mx_inner(const MxInnerArgs a) {
       const size_t i = s + 4 * size_t(p) + q;
       double xw[MG], yw[NG];
 #pragma unroll
-      for (int g = 0; g < MG; ++g) xw[g] = (xok[g] && i < a.n) ? double(xp[g][i]) * xsc[g] : 0.0;
+      for (int g = 0; g < MG; ++g) xw[g] = (x[g].ok && i < a.n) ? double(static_cast<const TX*>(x[g].p)[i]) * x[g].s : 0.0;
 #pragma unroll
-      for (int h = 0; h < NG; ++h) yw[h] = (yok[h] && i < a.n) ? double(yp[h][i]) * ysc[h] : 0.0;
-#pragma unroll
-      for (int g = 0; g < MG; ++g)
-#pragma unroll
-        for (int h = 0; h < NG; ++h) acc[g][h] = __builtin_amdgcn_mfma_f64_4x4x4f64(xw[g], yw[h], acc[g][h], 0, 0, 0);
+      for (int h = 0; h < NG; ++h) yw[h] = (y[h].ok && i < a.n) ? TileQuads<CP, NG>::elem(h, a.g64, y[h].p, i) * y[h].s : 0.0;
+      mac(xw, yw);
     }
   }
-
-  // Fold the 4 blocks (lane bits 2-3), then the 4 waves through LDS: k_gemm_inner's epilogue.
-  __shared__ double red[kBlock / 64][MG * NG][16];
-#pragma unroll
-  for (int g = 0; g < MG; ++g)
-#pragma unroll
-    for (int h = 0; h < NG; ++h) {
-      double v = acc[g][h];
-      v += __shfl_xor(v, 4, 64);
-      v += __shfl_xor(v, 8, 64);
-      if ((lane & 12) == 0) red[wave][g * NG + h][(lane >> 4) * 4 + (lane & 3)] = v;
-    }
-  __syncthreads();
-  const size_t mk = size_t(a.m) * a.k;
-  double* out = a.partial + size_t(blockIdx.x) * mk;
-  for (int s = threadIdx.x; s < MG * NG * 16; s += kBlock) {
-    const int gh = s >> 4, e = s & 15;
-    const int row = 4 * (gh / NG) + (e >> 2), col = 4 * (gh % NG) + (e & 3);
-    if (row < a.m && col < a.k) {
-      double v = red[0][gh][e];
-#pragma unroll
-      for (int w = 1; w < kBlock / 64; ++w) v += red[w][gh][e];
-      out[size_t(row) * a.k + col] = v;
-    }
-  }
-}
-
-// ---- gemm_inner over columns of both storage types ------------------------------------------------
-struct ColsInnerArgs {
-  const double* x[ssp::kInnerRows];  // rows (f64): MG groups of 4
-  const void* y[ssp::kInnerCols];    // column slots: NG groups of 4, the first g64 groups f64, the others f32;
-                                     // null: a padding slot (never the first of its group)
-  double xs[ssp::kInnerRows];
-  double ys[ssp::kInnerCols];
-  int m;
-  int k;    // slots, a multiple of 4
-  int g64;
-  size_t n;
-  double* partial;  // [gridDim.x][m][k]
-};
-static_assert(sizeof(ColsInnerArgs) <= 4000, "kernel argument block too large");
-
-
-// k_mx_inner<double, TY> with TY chosen per group of 4 columns (mx_cols_plan.h): group h of the tile is
-// f64 when h < g64, a wave-uniform branch, so one launch reads its rows once for the columns of both
-// types.  The chunk-to-wave mapping, the MFMA order (elements in increasing order per accumulator) and
-// the epilogue are k_mx_inner's.  Lanes of a padding slot read their group's first column; what they
-// accumulate is stored with the rest (the layout of the partials depends on the slots only) and dropped
-// by the host.
-// Registers: every group's quad has 16 bytes in lo[h] (an f32 quad, or the first half of an f64 one) and,
-// for the first H64 groups, the ones that can be f64, the 16 more of hi[h].  H64 = NG: any group may be
-// f64.  A lean form (H64 = 4: the 16 f64 columns of a subspace update, later groups f32 statically, the
-// register footprint of k_mx_inner<double, float>) measured no faster on the tile of 16 f64 + 48 f32
-// columns at N = 1.25e7 and 1e8 (profiles/r8/q32_fused.md), so it is not instantiated.
-template <int MG, int NG>
-__global__ __launch_bounds__(kBlock) void k_q32_inner_cols(const ColsInnerArgs a) {
-  constexpr int H64 = NG;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r = lane & 3, p = lane >> 2;
-  const int g64 = a.g64;
-  const double* xp[MG];
-  const char* yp[NG];
-  double xsc[MG], ysc[NG];
-  bool xok[MG], yok[NG];
-#pragma unroll
-  for (int g = 0; g < MG; ++g) {
-    xok[g] = 4 * g + r < a.m;
-    xp[g] = xok[g] ? a.x[4 * g + r] : a.x[4 * g < a.m ? 4 * g : 0];
-    xsc[g] = xok[g] ? a.xs[4 * g + r] : 1.0;
-  }
-#pragma unroll
-  for (int h = 0; h < NG; ++h) {
-    const void* c = 4 * h < a.k ? a.y[4 * h + r] : nullptr;
-    yok[h] = c != nullptr;
-    yp[h] = static_cast<const char*>(yok[h] ? c : a.y[4 * h < a.k ? 4 * h : 0]);
-    ysc[h] = yok[h] ? a.ys[4 * h + r] : 1.0;
-  }
-  double acc[MG][NG];
-#pragma unroll
-  for (int g = 0; g < MG; ++g)
-#pragma unroll
-    for (int h = 0; h < NG; ++h) acc[g][h] = 0;
-
-  const size_t gw = size_t(__builtin_amdgcn_readfirstlane(int(blockIdx.x * (kBlock / 64) + wave)));
-  const size_t nw = size_t(gridDim.x) * (kBlock / 64);
-  const size_t nchunks = a.n / 64;
-  for (size_t ch = gw; ch < nchunks; ch += nw) {
-    const size_t e0 = ch * 64 + 4 * size_t(p);
-    Raw<double> xv[MG];
-    nt_float4 lo[NG];
-    nt_double2 hi[H64];
-#pragma unroll
-    for (int g = 0; g < MG; ++g) xv[g] = 4 * g < a.m ? ldq<true>(xp[g] + e0) : zero_quad<double>();
-#pragma unroll
-    for (int h = 0; h < NG; ++h) {
-      lo[h] = nt_float4{0.f, 0.f, 0.f, 0.f};
-      if (h < H64) hi[h < H64 ? h : 0] = nt_double2{0., 0.};
-      if (4 * h < a.k) {
-        if (h < H64 && h < g64) {
-          const Raw<double> v = ldq<true>(reinterpret_cast<const double*>(yp[h]) + e0);
-          lo[h] = __builtin_bit_cast(nt_float4, v.a);
-          hi[h < H64 ? h : 0] = v.b;
-        } else {
-          lo[h] = ldq<true>(reinterpret_cast<const float*>(yp[h]) + e0).a;
-        }
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      double xw[MG], yw[NG];
-#pragma unroll
-      for (int g = 0; g < MG; ++g) xw[g] = xv[g].get(q) * xsc[g];
-#pragma unroll
-      for (int h = 0; h < NG; ++h) {
-        double v = double(lo[h][q]);
-        if (h < H64 && h < g64) v = q < 2 ? __builtin_bit_cast(nt_double2, lo[h])[q] : hi[h < H64 ? h : 0][q - 2];
-        yw[h] = v * ysc[h];
-      }
-#pragma unroll
-      for (int g = 0; g < MG; ++g)
-#pragma unroll
-        for (int h = 0; h < NG; ++h) acc[g][h] = __builtin_amdgcn_mfma_f64_4x4x4f64(xw[g], yw[h], acc[g][h], 0, 0, 0);
-    }
-  }
-  // Remainder [64 nchunks, n): guarded element loads, zeros past n.
-  for (size_t s = nchunks * 64 + gw * 64; s < a.n; s += nw * 64) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const size_t i = s + 4 * size_t(p) + q;
-      double xw[MG], yw[NG];
-#pragma unroll
-      for (int g = 0; g < MG; ++g) xw[g] = (4 * g < a.m && i < a.n) ? xp[g][i] * xsc[g] : 0.0;
-#pragma unroll
-      for (int h = 0; h < NG; ++h) {
-        double v = 0.0;
-        if (4 * h < a.k && i < a.n)
-          v = (h < H64 && h < g64) ? reinterpret_cast<const double*>(yp[h])[i]
-                                   : double(reinterpret_cast<const float*>(yp[h])[i]);
-        yw[h] = v * ysc[h];
-      }
-#pragma unroll
-      for (int g = 0; g < MG; ++g)
-#pragma unroll
-        for (int h = 0; h < NG; ++h) acc[g][h] = __builtin_amdgcn_mfma_f64_4x4x4f64(xw[g], yw[h], acc[g][h], 0, 0, 0);
-    }
-  }
-
-  // Fold the 4 blocks (lane bits 2-3), then the 4 waves through LDS: k_gemm_inner's epilogue.
-  __shared__ double red[kBlock / 64][MG * NG][16];
-#pragma unroll
-  for (int g = 0; g < MG; ++g)
-#pragma unroll
-    for (int h = 0; h < NG; ++h) {
-      double v = acc[g][h];
-      v += __shfl_xor(v, 4, 64);
-      v += __shfl_xor(v, 8, 64);
-      if ((lane & 12) == 0) red[wave][g * NG + h][(lane >> 4) * 4 + (lane & 3)] = v;
-    }
-  __syncthreads();
-  const size_t mk = size_t(a.m) * a.k;
-  double* out = a.partial + size_t(blockIdx.x) * mk;
-  for (int s = threadIdx.x; s < MG * NG * 16; s += kBlock) {
-    const int gh = s >> 4, e = s & 15;
-    const int row = 4 * (gh / NG) + (e >> 2), col = 4 * (gh % NG) + (e & 3);
-    if (row < a.m && col < a.k) {
-      double v = red[0][gh][e];
-#pragma unroll
-      for (int w = 1; w < kBlock / 64; ++w) v += red[w][gh][e];
-      out[size_t(row) * a.k + col] = v;
-    }
-  }
+  ssp::tile_store_partials<MG, NG>(acc, a.m, a.k, a.partial);
 }
 
 // ---- host side ------------------------------------------------------------------------------------
@@ -615,9 +471,18 @@ int check_vec(const void* p, size_t n, const char* what) {
 int check_ptrs(const void* const* v, int count, size_t n, const char* what) {
   if (count > 0 && !v) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null vector list");
   for (int i = 0; i < count; ++i) SSP_TRY(check_vec(v[i], n, what));
-  if (n > 0)
-    for (int i = 0; i < count; ++i)
-      if (!v[i]) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null vector");
+  return SSP_OK;
+}
+
+// The storage pair of a mixed call as types: launch(X, Y) gets a value of the first operand's storage type
+// and one of the second's (tags: only decltype(X), decltype(Y) are used) and launches the kernels of that
+// pair.  (f64, f64) never reaches here: every entry point forwards it to its f64 call.
+template <typename F>
+int with_pair(ssp_dtype tx, ssp_dtype ty, F&& launch) {
+  if (tx == SSP_F32 && ty == SSP_F32) launch(float(), float());
+  else if (tx == SSP_F32) launch(float(), double());
+  else launch(double(), float());
+  SSP_TRY_HIP(hipGetLastError());
   return SSP_OK;
 }
 
@@ -625,14 +490,11 @@ int check_ptrs(const void* const* v, int count, size_t n, const char* what) {
 int convert(ssp_ctx* ctx, void* x, ssp_dtype tx, const void* y, ssp_dtype ty, double ys, size_t n) {
   if (n == 0) return SSP_OK;
   const dim3 g(quad_grid(ctx, n, kMxU, 16)), b(kBlock);
-  if (tx == SSP_F32 && ty == SSP_F32)
-    SSP_LAUNCH((k_mx_copy<float, float>), g, b, 0, ctx->stream, static_cast<float*>(x), static_cast<const float*>(y), n, ys);
-  else if (tx == SSP_F32)
-    SSP_LAUNCH((k_mx_copy<float, double>), g, b, 0, ctx->stream, static_cast<float*>(x), static_cast<const double*>(y), n, ys);
-  else  // (f64, f64) never reaches here: ssp_mx_copy forwards it to ssp_copy / ssp_scal_copy
-    SSP_LAUNCH((k_mx_copy<double, float>), g, b, 0, ctx->stream, static_cast<double*>(x), static_cast<const float*>(y), n, ys);
-  SSP_TRY_HIP(hipGetLastError());
-  return SSP_OK;
+  return with_pair(tx, ty, [&](auto X, auto Y) {
+    using TX = decltype(X);
+    using TY = decltype(Y);
+    SSP_LAUNCH((k_mx_copy<TX, TY>), g, b, 0, ctx->stream, static_cast<TX*>(x), static_cast<const TY*>(y), n, ys);
+  });
 }
 
 // Scratch f64 vectors of the exact path (vectors of at most exact_max elements): an f32 operand widened
@@ -669,32 +531,29 @@ struct Scratch {
   }
 };
 
-template <typename TX, typename TY, int MG>
-int launch_inner_ng(ssp_ctx* ctx, unsigned grid, const MxInnerArgs& a) {
+// The ladder of k_mx_inner over (MG, NG): the smallest instantiated tile that holds a.m rows and a.k columns.
+template <typename TX, typename CP, int MG>
+void launch_inner_ng(ssp_ctx* ctx, unsigned grid, const MxInnerArgs& a) {
   const int need = (a.k + 3) / 4;
   const dim3 g(grid), b(kBlock);
-  if (need <= 1) SSP_LAUNCH((k_mx_inner<TX, TY, MG, 1>), g, b, 0, ctx->stream, a);
-  else if (need <= 2) SSP_LAUNCH((k_mx_inner<TX, TY, MG, 2>), g, b, 0, ctx->stream, a);
-  else if (need <= 4) SSP_LAUNCH((k_mx_inner<TX, TY, MG, 4>), g, b, 0, ctx->stream, a);
-  else if (need <= 8) SSP_LAUNCH((k_mx_inner<TX, TY, MG, 8>), g, b, 0, ctx->stream, a);
-  else if (need <= 12) SSP_LAUNCH((k_mx_inner<TX, TY, MG, 12>), g, b, 0, ctx->stream, a);
-  else SSP_LAUNCH((k_mx_inner<TX, TY, MG, 16>), g, b, 0, ctx->stream, a);
-  SSP_TRY_HIP(hipGetLastError());
-  return SSP_OK;
+  if (need <= 1) SSP_LAUNCH((k_mx_inner<TX, CP, MG, 1>), g, b, 0, ctx->stream, a);
+  else if (need <= 2) SSP_LAUNCH((k_mx_inner<TX, CP, MG, 2>), g, b, 0, ctx->stream, a);
+  else if (need <= 4) SSP_LAUNCH((k_mx_inner<TX, CP, MG, 4>), g, b, 0, ctx->stream, a);
+  else if (need <= 8) SSP_LAUNCH((k_mx_inner<TX, CP, MG, 8>), g, b, 0, ctx->stream, a);
+  else if (need <= 12) SSP_LAUNCH((k_mx_inner<TX, CP, MG, 12>), g, b, 0, ctx->stream, a);
+  else SSP_LAUNCH((k_mx_inner<TX, CP, MG, 16>), g, b, 0, ctx->stream, a);
 }
 
-template <typename TX, typename TY>
-int launch_inner_mg(ssp_ctx* ctx, unsigned grid, const MxInnerArgs& a) {
+template <typename TX, typename CP>
+void launch_inner_mg(ssp_ctx* ctx, unsigned grid, const MxInnerArgs& a) {
   const int mg = (a.m + 3) / 4;
-  if (mg <= 1) return launch_inner_ng<TX, TY, 1>(ctx, grid, a);
-  if (mg <= 2) return launch_inner_ng<TX, TY, 2>(ctx, grid, a);
-  return launch_inner_ng<TX, TY, 4>(ctx, grid, a);
+  if (mg <= 1) launch_inner_ng<TX, CP, 1>(ctx, grid, a);
+  else if (mg <= 2) launch_inner_ng<TX, CP, 2>(ctx, grid, a);
+  else launch_inner_ng<TX, CP, 4>(ctx, grid, a);
 }
 
 int launch_inner(ssp_ctx* ctx, unsigned grid, const MxInnerArgs& a, ssp_dtype tr, ssp_dtype tc) {
-  if (tr == SSP_F32 && tc == SSP_F32) return launch_inner_mg<float, float>(ctx, grid, a);
-  if (tr == SSP_F32) return launch_inner_mg<float, double>(ctx, grid, a);
-  return launch_inner_mg<double, float>(ctx, grid, a);
+  return with_pair(tr, tc, [&](auto X, auto Y) { launch_inner_mg<decltype(X), decltype(Y)>(ctx, grid, a); });
 }
 
 // One wave per chunk of 64 elements, at most ctx->inner_per_cu workgroups per CU (k_gemm_inner's grid).
@@ -714,40 +573,47 @@ void launch_outer_m(ssp_ctx* ctx, unsigned grid, const MxOuterArgs& a) {
   else SSP_LAUNCH((k_mx_outer<TX, TY, 16, SET>), g, b, 0, ctx->stream, a);
 }
 
-template <typename TX, typename TY>
-void launch_outer_t(ssp_ctx* ctx, unsigned grid, const MxOuterArgs& a, bool set) {
-  set ? launch_outer_m<TX, TY, true>(ctx, grid, a) : launch_outer_m<TX, TY, false>(ctx, grid, a);
-}
-
-int launch_outer(ssp_ctx* ctx, const MxOuterArgs& a, ssp_dtype tx, ssp_dtype ty, bool set) {
+// yy[j] = (set ? 0 : ys[j] yy[j]) + sum_i alphas(i, j) (xs[i] xx[i]) on the bandwidth path (k, m, n > 0).
+// Destinations are independent, kOuterDst per launch; sources are applied in increasing order, kOuterSrc per
+// launch, so each destination sees the reference's summation order (an f32 destination is rounded per launch).
+// xs, ys: null for none; the destinations' scales ride along with the first source chunk, and not with set.
+int outer_chunks(ssp_ctx* ctx, const double* alphas, const void* const* xx, ssp_dtype tx, const double* xs, int k,
+                 void* const* yy, ssp_dtype ty, const double* ys, int m, size_t n, bool set) {
   // one wave per window of 2 x 64 quads, ctx->outer_per_cu workgroups per CU (SSP_OUTER_WG_PER_CU)
-  const unsigned grid = ssp::stream_grid(ctx, a.n / 4 + 1, 2, unsigned(ctx->outer_per_cu));
-  if (tx == SSP_F32 && ty == SSP_F32) launch_outer_t<float, float>(ctx, grid, a, set);
-  else if (tx == SSP_F32) launch_outer_t<float, double>(ctx, grid, a, set);
-  else launch_outer_t<double, float>(ctx, grid, a, set);
-  SSP_TRY_HIP(hipGetLastError());
+  const unsigned grid = ssp::stream_grid(ctx, n / 4 + 1, 2, unsigned(ctx->outer_per_cu));
+  const auto staged = [&](const double* v, size_t count, const double** dev) {
+    void* p;
+    SSP_TRY(ssp::upload_small(ctx, v, count * sizeof(double), &p));
+    *dev = static_cast<const double*>(p);
+    return int(SSP_OK);
+  };
+  for (int j0 = 0; j0 < m; j0 += ssp::kOuterDst) {
+    const int mm = std::min(ssp::kOuterDst, m - j0);
+    for (int i0 = 0; i0 < k; i0 += ssp::kOuterSrc) {
+      MxOuterArgs a{};
+      a.m = mm;
+      a.k = std::min(ssp::kOuterSrc, k - i0);
+      a.n = n;
+      for (int i = 0; i < a.k; ++i) a.x[i] = xx[i0 + i];
+      for (int j = 0; j < mm; ++j) a.y[j] = yy[j0 + j];
+      if (xs) SSP_TRY(staged(xs + i0, size_t(a.k), &a.scale_dev));
+      if (ys && !set && i0 == 0) SSP_TRY(staged(ys + j0, size_t(mm), &a.yscale_dev));
+      const bool dev = a.k * mm > ssp::kOuterAlpha;
+      std::vector<double> block(dev ? size_t(a.k) * mm : 0);
+      double* dst = dev ? block.data() : a.alpha;
+      for (int i = 0; i < a.k; ++i)
+        for (int j = 0; j < mm; ++j) dst[i * mm + j] = alphas[size_t(i0 + i) * m + j0 + j];
+      if (dev) SSP_TRY(staged(block.data(), block.size(), &a.alpha_dev));
+      SSP_TRY(ssp::flush_uploads(ctx));
+      const bool first = set && i0 == 0;  // the launch that writes the destinations without reading them
+      SSP_TRY(with_pair(tx, ty, [&](auto X, auto Y) {
+        using TX = decltype(X);
+        using TY = decltype(Y);
+        first ? launch_outer_m<TX, TY, true>(ctx, grid, a) : launch_outer_m<TX, TY, false>(ctx, grid, a);
+      }));
+    }
+  }
   return SSP_OK;
-}
-
-template <int MG>
-int launch_cols_ng(ssp_ctx* ctx, unsigned grid, const ColsInnerArgs& a) {
-  const int need = a.k / 4;
-  const dim3 g(grid), b(kBlock);
-  if (need <= 1) SSP_LAUNCH((k_q32_inner_cols<MG, 1>), g, b, 0, ctx->stream, a);
-  else if (need <= 2) SSP_LAUNCH((k_q32_inner_cols<MG, 2>), g, b, 0, ctx->stream, a);
-  else if (need <= 4) SSP_LAUNCH((k_q32_inner_cols<MG, 4>), g, b, 0, ctx->stream, a);
-  else if (need <= 8) SSP_LAUNCH((k_q32_inner_cols<MG, 8>), g, b, 0, ctx->stream, a);
-  else if (need <= 12) SSP_LAUNCH((k_q32_inner_cols<MG, 12>), g, b, 0, ctx->stream, a);
-  else SSP_LAUNCH((k_q32_inner_cols<MG, 16>), g, b, 0, ctx->stream, a);
-  SSP_TRY_HIP(hipGetLastError());
-  return SSP_OK;
-}
-
-int launch_cols(ssp_ctx* ctx, unsigned grid, const ColsInnerArgs& a) {
-  const int mg = (a.m + 3) / 4;
-  if (mg <= 1) return launch_cols_ng<1>(ctx, grid, a);
-  if (mg <= 2) return launch_cols_ng<2>(ctx, grid, a);
-  return launch_cols_ng<4>(ctx, grid, a);
 }
 
 }  // namespace
@@ -784,38 +650,24 @@ int q32_dense_pass(ssp_ctx* ctx, const double* alphas, const float* const* xx, i
   LedgerScope ls(ctx, "gemm_outer_f32", (4.0 * k + (set ? 1.0 : 2.0) * 8.0 * m) * n);
   bool scaled = false;
   for (int j = 0; !set && ys && j < m; ++j) scaled = scaled || ys[j] != 1.0;
-  for (int j0 = 0; j0 < m; j0 += kOuterDst) {
-    const int mm = std::min(kOuterDst, m - j0);
-    for (int i0 = 0; i0 < k; i0 += kOuterSrc) {
-      MxOuterArgs a{};
-      a.m = mm;
-      a.k = std::min(kOuterSrc, k - i0);
-      a.n = n;
-      for (int i = 0; i < a.k; ++i) a.x[i] = xx[i0 + i];
-      for (int j = 0; j < mm; ++j) a.y[j] = yy[j0 + j];
-      if (scaled && i0 == 0) {
-        void* ps;
-        SSP_TRY(upload_small(ctx, ys + j0, size_t(mm) * sizeof(double), &ps));
-        a.yscale_dev = static_cast<const double*>(ps);
-      }
-      const bool dev = a.k * mm > kOuterAlpha;
-      std::vector<double> block(dev ? size_t(a.k) * mm : 0);
-      double* dst = dev ? block.data() : a.alpha;
-      for (int i = 0; i < a.k; ++i)
-        for (int j = 0; j < mm; ++j) dst[i * mm + j] = alphas[size_t(i0 + i) * m + j0 + j];
-      if (dev) {
-        void* p;
-        SSP_TRY(upload_small(ctx, block.data(), block.size() * sizeof(double), &p));
-        a.alpha_dev = static_cast<const double*>(p);
-      }
-      SSP_TRY(flush_uploads(ctx));
-      SSP_TRY(launch_outer(ctx, a, SSP_F32, SSP_F64, set && i0 == 0));
-    }
-  }
-  return SSP_OK;
+  return outer_chunks(ctx, alphas, reinterpret_cast<const void* const*>(xx), SSP_F32, nullptr, k,
+                      reinterpret_cast<void* const*>(yy), SSP_F64, scaled ? ys : nullptr, m, n, set);
 }
 
 }  // namespace ssp
+
+// The library's dynamic symbol list also holds the weak out-of-line copies of the HIP launch templates that
+// the compiler happened not to inline.  k_mx_axpy's three were such; inside with_pair's callable they are
+// inlined, so they are instantiated here to leave the list as it was.
+#define SSP_KEEP_LAUNCH(TX, TY)                                                                                       \
+  template void hipExtLaunchKernelGGL<const TX*, TY*, size_t, double>(void (*)(const TX*, TY*, size_t, double),       \
+                                                                      const dim3&, const dim3&, std::uint32_t,        \
+                                                                      hipStream_t, hipEvent_t, hipEvent_t,            \
+                                                                      std::uint32_t, const TX*, TY*, size_t, double)
+SSP_KEEP_LAUNCH(float, float);
+SSP_KEEP_LAUNCH(float, double);
+SSP_KEEP_LAUNCH(double, float);
+#undef SSP_KEEP_LAUNCH
 
 extern "C" {
 
@@ -879,7 +731,7 @@ int ssp_q32_gemm_inner_cols(ssp_ctx* ctx, const double* const* xx, const double*
     const unsigned grid = inner_grid(ctx, n);
     for (size_t t = 0; t < plan.tiles.size(); ++t) {
       const ssp::ColsTile& tile = plan.tiles[t];
-      ColsInnerArgs a{};
+      MxInnerArgs a{};
       a.m = tile.rows;
       a.k = tile.cols;
       a.g64 = tile.g64;
@@ -895,25 +747,11 @@ int ssp_q32_gemm_inner_cols(ssp_ctx* ctx, const double* const* xx, const double*
       }
       SSP_TRY(ssp::ensure_partial(ctx, size_t(grid) * a.m * a.k));
       a.partial = ctx->partial;
-      if (tile.g64 == 0) {
-        // a tile of f32 columns only: k_mx_inner<double, float>, the same partials (a padding slot
-        // repeats its group's first column: computed, never read back)
-        MxInnerArgs b{};
-        b.m = a.m;
-        b.k = a.k;
-        b.n = n;
-        b.partial = a.partial;
-        for (int i = 0; i < a.m; ++i) {
-          b.x[i] = a.x[i];
-          b.xs[i] = a.xs[i];
-        }
-        for (int j = 0; j < a.k; ++j) {
-          b.y[j] = a.y[j] ? a.y[j] : a.y[j & ~3];
-          b.ys[j] = a.ys[j];
-        }
-        SSP_TRY((launch_inner_mg<double, float>(ctx, grid, b)));
+      if (tile.g64 == 0) {  // a tile of f32 columns only: the statically typed kernel on the same arguments
+        SSP_TRY(launch_inner(ctx, grid, a, SSP_F64, SSP_F32));
       } else {
-        SSP_TRY(launch_cols(ctx, grid, a));
+        launch_inner_mg<double, ByGroup>(ctx, grid, a);
+        SSP_TRY_HIP(hipGetLastError());
       }
       SSP_TRY(ssp::launch_reduce_partials(ctx, ctx->partial, int(grid), a.m, a.k, ctx->result_dev, S, tile.r0, tile.c0,
                                           &tail, t + 1 == plan.tiles.size()));
@@ -1010,14 +848,11 @@ int ssp_mx_axpy(ssp_ctx* ctx, double alpha, const void* x, ssp_dtype tx, void* y
   }
   ssp::LedgerScope ls(ctx, "axpy_f32", (esize(tx) + 2 * esize(ty)) * n);
   const dim3 g(quad_grid(ctx, n, kMxU, 16)), b(kBlock);
-  if (tx == SSP_F32 && ty == SSP_F32)
-    SSP_LAUNCH((k_mx_axpy<float, float>), g, b, 0, ctx->stream, static_cast<const float*>(x), static_cast<float*>(y), n, alpha);
-  else if (tx == SSP_F32)
-    SSP_LAUNCH((k_mx_axpy<float, double>), g, b, 0, ctx->stream, static_cast<const float*>(x), static_cast<double*>(y), n, alpha);
-  else
-    SSP_LAUNCH((k_mx_axpy<double, float>), g, b, 0, ctx->stream, static_cast<const double*>(x), static_cast<float*>(y), n, alpha);
-  SSP_TRY_HIP(hipGetLastError());
-  return SSP_OK;
+  return with_pair(tx, ty, [&](auto X, auto Y) {
+    using TX = decltype(X);
+    using TY = decltype(Y);
+    SSP_LAUNCH((k_mx_axpy<TX, TY>), g, b, 0, ctx->stream, static_cast<const TX*>(x), static_cast<TY*>(y), n, alpha);
+  });
 }
 
 int ssp_mx_dot(ssp_ctx* ctx, const void* x, ssp_dtype tx, const void* y, ssp_dtype ty, size_t n, double* out) {
@@ -1042,14 +877,12 @@ int ssp_mx_dot(ssp_ctx* ctx, const void* x, ssp_dtype tx, const void* y, ssp_dty
   {
     ssp::LedgerScope ls(ctx, "dot_f32", (esize(tx) + esize(ty)) * n);
     const dim3 g(grid), b(kBlock);
-    double* part = ctx->partial;
-    if (tx == SSP_F32 && ty == SSP_F32)
-      SSP_LAUNCH((k_mx_dot<float, float>), g, b, 0, ctx->stream, static_cast<const float*>(x), static_cast<const float*>(y), n, part, tail);
-    else if (tx == SSP_F32)
-      SSP_LAUNCH((k_mx_dot<float, double>), g, b, 0, ctx->stream, static_cast<const float*>(x), static_cast<const double*>(y), n, part, tail);
-    else
-      SSP_LAUNCH((k_mx_dot<double, float>), g, b, 0, ctx->stream, static_cast<const double*>(x), static_cast<const float*>(y), n, part, tail);
-    SSP_TRY_HIP(hipGetLastError());
+    SSP_TRY(with_pair(tx, ty, [&](auto X, auto Y) {
+      using TX = decltype(X);
+      using TY = decltype(Y);
+      SSP_LAUNCH((k_mx_dot<TX, TY>), g, b, 0, ctx->stream, static_cast<const TX*>(x), static_cast<const TY*>(y), n,
+                 ctx->partial, tail);
+    }));
   }
   return ssp::fold_finish(ctx, tail, out);
 }
@@ -1162,40 +995,10 @@ int ssp_mx_gemm_outer(ssp_ctx* ctx, const double* alphas, const void* const* xx,
     for (int j = 0; ty == SSP_F32 && j < m; ++j) SSP_TRY(convert(ctx, yy[j], SSP_F32, yw[size_t(j)], SSP_F64, 1.0, n));
     return SSP_OK;
   }
-  // Destinations are independent; sources are applied in increasing order, kOuterSrc per launch, so
-  // each destination sees the reference's summation order (an f32 destination is rounded per launch).
   ssp::LedgerScope ls(ctx, "gemm_outer_f32", (esize(tx) * k + (set ? 1.0 : 2.0) * esize(ty) * m) * n);
   bool scaled = false;
   for (int i = 0; xs && i < k; ++i) scaled = scaled || xs[i] != 1.0;
-  for (int j0 = 0; j0 < m; j0 += ssp::kOuterDst) {
-    const int mm = std::min(ssp::kOuterDst, m - j0);
-    for (int i0 = 0; i0 < k; i0 += ssp::kOuterSrc) {
-      MxOuterArgs a{};
-      a.m = mm;
-      a.k = std::min(ssp::kOuterSrc, k - i0);
-      a.n = n;
-      for (int i = 0; i < a.k; ++i) a.x[i] = xx[i0 + i];
-      for (int j = 0; j < mm; ++j) a.y[j] = yy[j0 + j];
-      if (scaled) {
-        void* ps;
-        SSP_TRY(ssp::upload_small(ctx, xs + i0, size_t(a.k) * sizeof(double), &ps));
-        a.scale_dev = static_cast<const double*>(ps);
-      }
-      const bool dev = a.k * mm > ssp::kOuterAlpha;
-      std::vector<double> block(dev ? size_t(a.k) * mm : 0);
-      double* dst = dev ? block.data() : a.alpha;
-      for (int i = 0; i < a.k; ++i)
-        for (int j = 0; j < mm; ++j) dst[i * mm + j] = alphas[size_t(i0 + i) * m + j0 + j];
-      if (dev) {
-        void* p;
-        SSP_TRY(ssp::upload_small(ctx, block.data(), block.size() * sizeof(double), &p));
-        a.alpha_dev = static_cast<const double*>(p);
-      }
-      SSP_TRY(ssp::flush_uploads(ctx));
-      SSP_TRY(launch_outer(ctx, a, tx, ty, set && i0 == 0));
-    }
-  }
-  return SSP_OK;
+  return outer_chunks(ctx, alphas, xx, tx, scaled ? xs : nullptr, k, yy, ty, nullptr, m, n, set != 0);
 }
 
 }  // extern "C"

@@ -173,7 +173,10 @@ __global__ __launch_bounds__(kBlock) void k_gemm_inner(const InnerArgs a) {
     }
   }
 
-  // Fold the 4 blocks (lane bits 2-3), then the 4 waves through LDS.
+  // Fold the 4 blocks (lane bits 2-3), then the 4 waves through LDS.  This is a second copy of
+  // ssp::tile_store_partials (mfma_tile.h, the epilogue of the mixed-precision tile kernel): calling it here
+  // changed this file's device assembly (the address arithmetic of the LDS stores, the place of the
+  // barrier), so the f64 kernel keeps its own text.  A change to either goes into both.
   __shared__ double red[kBlock / 64][MG * NG][16];
 #pragma unroll
   for (int g = 0; g < MG; ++g)
