@@ -108,12 +108,42 @@ int itsolv_diis_synth(ssp_ctx* ctx, size_t n, const sspx_synth* spec, const itso
  * LinearEigensystemDavidson<Vec, VecF32, SparseP> over make_handlers_q32()): R vectors, the subspace
  * matrices and every kernel's arithmetic stay f64; a Q vector is rounded once, to nearest-even, when it
  * is stored.  Half the HBM per Q vector and half the bytes of every pass over the Q space.  Eigenvalues
- * move by at most about 4 eps32 |H| (first-order perturbation of the stored vectors), so convergence
- * thresholds down to about 1e-6 |H| are meaningful; same arguments and results as the f64 entries. */
+ * move by at most about 4 eps32 |H| (first-order perturbation of the stored vectors), and the residual
+ * the solver estimates from the stored pairs floors near eps32 |a|: with these two entries convergence
+ * thresholds down to about 1e-6 |H| are meaningful (below, the solve stalls; use the refined entries).
+ * Same arguments and results as the f64 entries. */
 int itsolv_davidson_dense_q32(ssp_ctx* ctx, const double* h, size_t n, const itsolv_options* opt, itsolv_result* out,
                               double* solutions_out);
 int itsolv_davidson_synth_q32(ssp_ctx* ctx, size_t n, const sspx_synth* spec, const itsolv_options* opt,
                               itsolv_result* out, double* solutions_out);
+
+/* The same two solves in the REFINED mode of the f32 Q space (itsolv_hbm/solvers.h set_refine), which reaches
+ * f64 thresholds (1e-8, 1e-10) with the Q space still in 4 bytes per element:
+ *   1. a new parameter vector is rounded to f32-representable values (ssp_quantise_f32) BEFORE its action
+ *      is computed, so the stored vector is exact and the action belongs to it;
+ *   2. the new rows of the subspace H come from the stored Q parameters and the new f64 actions, not from
+ *      the stored f32 actions: S and H are the exact f64 projection onto the span of the stored vectors;
+ *   3. only the stored actions then carry error, bounded for root i by
+ *      delta_i = 2^-24 sum_j |c_ji| |a_j|.  A root whose residual estimate is <= max(kappa delta_i,
+ *      threshold + delta_i) has its residual recomputed from the action of its solution.
+ * The price: until that point a root costs nothing extra; from it on, ONE MORE ACTION per such root and
+ * iteration (all refined roots of an iteration in one action call; a converged root stays among them, as
+ * the solver recomputes every root's residual in every iteration).  The errors reported for converged
+ * roots are then true residual norms, not estimates.
+ * Scope: hermitian = 1 only; max_size_qspace, reset_D and reset_D_max_Q_size must be unset (a D space holds
+ * rounded combinations whose pairs are inconsistent in the way step 1 removes for Q); each is refused with
+ * an error that names the option.  refine: NULL for the defaults; kappa <= 0 means the default of 8. */
+typedef struct {
+  double kappa;
+} itsolv_q32_refine;
+int itsolv_davidson_dense_q32_refined(ssp_ctx* ctx, const double* h, size_t n, const itsolv_options* opt,
+                                      const itsolv_q32_refine* refine, itsolv_result* out, double* solutions_out);
+int itsolv_davidson_synth_q32_refined(ssp_ctx* ctx, size_t n, const sspx_synth* spec, const itsolv_options* opt,
+                                      const itsolv_q32_refine* refine, itsolv_result* out, double* solutions_out);
+/* What the calling thread's last refined solve spent (thread-local, as itsolv_last_error): actions on refined
+ * residuals, the iteration (from 1; 0: none) of the first, the largest of the roots' last delta.  Any
+ * pointer may be NULL.  Returns 0. */
+int itsolv_q32_refine_stats(int* refined_actions, int* first_refined_iteration, double* max_delta);
 
 /* DIIS on r(x) = H (x - 1) for a dense row-major H (reference test_NonLinearEquations.cpp:38-49). */
 /* LinearEquationsDavidson (reference itsolv/LinearEquationsDavidson.h): A x_r = b_r for nrhs

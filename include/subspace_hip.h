@@ -292,7 +292,7 @@ int ssp_block_update(ssp_ctx* ctx, const double* palphas, const size_t* ptr, con
  *          fills of the context.
  *      All vectors of one side of a call share that side's dtype; pointers must be 16-byte aligned.
  *      (SSP_F64, SSP_F64) forwards to the f64 entry point.  Ledger names: copy_f32, axpy_f32, dot_f32,
- *      fill_f32, scal_f32, gemm_inner_f32, gemm_outer_f32; bytes count 4 per f32 and 8 per f64 element. */
+ *      fill_f32, scal_f32, quantise_f32, gemm_inner_f32, gemm_outer_f32; bytes count 4 per f32 and 8 per f64 element. */
 typedef enum { SSP_F64 = 0, SSP_F32 = 1 } ssp_dtype;
 /* n floats from the arena of ssp_alloc (4 n bytes, 256-byte aligned) */
 int ssp_alloc_f32(ssp_ctx* ctx, size_t n, float** out);
@@ -305,6 +305,13 @@ int ssp_fill_f32(ssp_ctx* ctx, double alpha, float* x, size_t n);
 int ssp_scal_f32(ssp_ctx* ctx, double alpha, float* x, size_t n);
 /* x[:] = (tx)(ys * y[:]), the product rounded to f64 first (ys = 1: a plain convert) */
 int ssp_mx_copy(ssp_ctx* ctx, void* x, ssp_dtype tx, const void* y, ssp_dtype ty, double ys, size_t n);
+/* xx[v][:] = (double)(float)(xs[v] * xx[v][:]) for m f64 vectors, in place and in one launch per 16 vectors:
+ * each element becomes the value ssp_mx_copy (F32 <- F64, ys = xs[v]) would store, widened again, so that a
+ * later narrowing copy of the vector is exact (the refined f32 Q space of itsolv_hbm.h quantises a new
+ * parameter vector BEFORE its action is computed).  xs may be null (all 1); a deferred scale costs no pass
+ * of its own.  The same kernel, and the same bits, at every length (exact_max is not looked at); n = 0 and
+ * m = 0 return at once.  Ledger name quantise_f32, 16 bytes per element and vector. */
+int ssp_quantise_f32(ssp_ctx* ctx, double* const* xx, const double* xs, int m, size_t n);
 /* y[:] = (ty)fma(alpha, x[:], y[:]) */
 int ssp_mx_axpy(ssp_ctx* ctx, double alpha, const void* x, ssp_dtype tx, void* y, ssp_dtype ty, size_t n);
 int ssp_mx_dot(ssp_ctx* ctx, const void* x, ssp_dtype tx, const void* y, ssp_dtype ty, size_t n, double* out);

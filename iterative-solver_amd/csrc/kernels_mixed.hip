@@ -12,7 +12,7 @@
 // kernel moves 512 N.
 //
 // Kernels.  k_mx_copy, k_mx_axpy, k_mx_scal, k_mx_dot: one per-element operation each, over map_quads;
-// k_mx_fill; k_mx_outer<TX, TY, M, SET> (gemm_outer, launched chunk by chunk from outer_chunks, also the
+// k_quantise_f32 (f64 vectors rounded through f32 in place, up to 16 per launch); k_mx_fill; k_mx_outer<TX, TY, M, SET> (gemm_outer, launched chunk by chunk from outer_chunks, also the
 // dense pass of the ssp_q32_* updates); k_mx_inner<TX, CP, MG, NG> (gemm_inner: the one MFMA tile kernel,
 // CP the columns' storage -- float, double, or ByGroup for ssp_q32_gemm_inner_cols).  with_pair maps the
 // storage pair of a call to the kernel's types.
@@ -200,6 +200,22 @@ __global__ __launch_bounds__(kBlock) void k_mx_dot(const TX* __restrict__ x, con
   const double s = ssp::block_sum256((acc[0] + acc[1]) + (acc[2] + acc[3]));
   if (threadIdx.x == 0) ssp::store_partial(partial + blockIdx.x, s);
   ssp::fold_tail(partial, tail);
+}
+
+// ---- quantise -------------------------------------------------------------------------------------
+struct QuantArgs {
+  double* x[ssp::kPrecVec];
+  double s[ssp::kPrecVec];
+  size_t n;
+};
+
+// x[v] = (double)(float)(x[v] * s[v]) in place, vector blockIdx.y: the value k_mx_copy<float, double> with
+// ys = s[v] would store, widened again, so the later narrowing copy of the result is exact.  The same kernel
+// at every length (a rounding has no summation order to keep).
+__global__ __launch_bounds__(kBlock) void k_quantise_f32(const QuantArgs a) {
+  double* const x = a.x[blockIdx.y];
+  const double s = a.s[blockIdx.y];
+  map_quads(a.n, x, [=](int, double v) { return double(float(v * s)); }, static_cast<const double*>(x));
 }
 
 // ---- gemm_outer -----------------------------------------------------------------------------------
@@ -826,6 +842,26 @@ int ssp_mx_copy(ssp_ctx* ctx, void* x, ssp_dtype tx, const void* y, ssp_dtype ty
   }
   ssp::LedgerScope ls(ctx, "copy_f32", (esize(tx) + esize(ty)) * n);
   return convert(ctx, x, tx, y, ty, ys, n);
+}
+
+int ssp_quantise_f32(ssp_ctx* ctx, double* const* xx, const double* xs, int m, size_t n) {
+  SSP_CHECK_CTX(ctx);  // pending zero fills are stored: every vector is read
+  if (m < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_quantise_f32: negative dimension");
+  if (m == 0 || n == 0) return SSP_OK;
+  SSP_TRY(check_ptrs(reinterpret_cast<const void* const*>(xx), m, n, "ssp_quantise_f32"));
+  ssp::LedgerScope ls(ctx, "quantise_f32", 16.0 * m * n);
+  for (int v0 = 0; v0 < m; v0 += ssp::kPrecVec) {
+    QuantArgs a{};
+    const int mm = std::min(ssp::kPrecVec, m - v0);
+    for (int v = 0; v < mm; ++v) {
+      a.x[v] = xx[v0 + v];
+      a.s[v] = xs ? xs[v0 + v] : 1.0;
+    }
+    a.n = n;
+    SSP_LAUNCH(k_quantise_f32, dim3(quad_grid(ctx, n, kMxU, 16), unsigned(mm)), dim3(kBlock), 0, ctx->stream, a);
+    SSP_TRY_HIP(hipGetLastError());
+  }
+  return SSP_OK;
 }
 
 int ssp_mx_axpy(ssp_ctx* ctx, double alpha, const void* x, ssp_dtype tx, void* y, ssp_dtype ty, size_t n) {

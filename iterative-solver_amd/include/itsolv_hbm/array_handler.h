@@ -412,6 +412,16 @@ bool fused_residual_norms(H&, const std::vector<double>&, const RefX&, const Ref
   return false;
 }
 
+// Hook for solvers whose Q vectors are stored in a narrower format than their R vectors (the refined
+// mode of IterativeSolverTemplate): rounds each of `xx` in place to the values its copy into a Q vector
+// (`qr`, the Q x R handler's copy) would store, so that the copy made later is exact and an action
+// computed in between belongs to the stored vector.  Returns false, touching nothing, when R and Q
+// store the same format.  Found by argument-dependent lookup.
+template <class H, class RefR>
+bool quantise_for_storage(H&, const RefR&) {
+  return false;
+}
+
 // Hook for a fused sequential self-orthonormalisation of R (reference propose_rspace.h:450-465):
 // returns false when the handler has no fused form (the caller then runs the reference loop of
 // dot / scal / dot / axpy calls).  Found by argument-dependent lookup.

@@ -414,6 +414,22 @@ inline bool fused_overlap_rows_mixed(array::ArrayHandler<Vec, VecF32>&, const it
   return true;
 }
 
+// R vectors rounded in place to the values their narrowing copy into the Q space stores
+// (array::quantise_for_storage hook, the refined mode of solvers.h): one ssp_quantise_f32 for all of them, a
+// pending normalisation scale applied as the vector is loaded.  What qr().copy() makes of the result is exact.
+inline bool quantise_for_storage(array::ArrayHandler<VecF32, Vec>&, const itsolv::VecRef<Vec>& xx) {
+  if (xx.empty()) return true;
+  const Vec& x0 = xx.front().get();
+  for (auto& x : xx)
+    if (!x.get().compatible(x0))
+      throw array::util::ArrayHandlerError{"quantise_for_storage: arrays have different distributions"};
+  std::vector<double> xs;
+  auto xp = detail::rw_deferred_ptrs(xx, xs);
+  check(ssp_quantise_f32(x0.ctx(), xp.data(), xs.data(), int(xx.size()), x0.local_size()), "ssp_quantise_f32");
+  detail::scales_applied(xx);
+  return true;
+}
+
 // New Q vectors as linear combinations of existing ones (array::fused_new_combinations hook,
 // construct_dspace): allocated without a copy and written by one write-only f32 -> f32 gemm_outer, each
 // element the f64 sum of its sources in order, rounded once.

@@ -159,12 +159,24 @@ void extract_solution_batches(Solver& solver, std::vector<R>& params, std::vecto
   }
 }
 
+// What a solve in the refined mode (solvers.h set_refine) spent: actions on refined residuals, the iteration
+// (from 1; 0: none) of the first, and the largest of the roots' last error bounds delta.
+struct RefineStats {
+  int refined_actions = 0;
+  int first_refined_iteration = 0;
+  double max_delta = 0;
+};
+
+// refine_kappa: null for the plain solve; else the refined mode with that kappa (<= 0: the default), and
+// refine_stats (optional) filled after the solve.
 template <class R, class Q, class P>
 void run_davidson(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Problem<R, P>& problem,
                   const std::function<R()>& make_vec, const std::function<double(const R&, double)>& residual_norm,
                   const itsolv_options& o, itsolv_result& out, const std::function<void(size_t, const R&)>& emit,
-                  const ResidualNormsBatch<R>& residual_norms_batch = {}) {
+                  const ResidualNormsBatch<R>& residual_norms_batch = {}, const double* refine_kappa = nullptr,
+                  RefineStats* refine_stats = nullptr) {
   LinearEigensystemDavidson<R, Q, P> solver(handlers);
+  if (refine_kappa) solver.set_refine(true, *refine_kappa);
   LinearEigensystemDavidsonOptions opt;
   apply_options(o, opt);
   if (o.max_size_qspace > 0) opt.max_size_qspace = o.max_size_qspace;
@@ -188,6 +200,12 @@ void run_davidson(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Proble
   out.host_algebra_seconds = dense::AlgebraClock::seconds;
   out.host_algebra_calls = dense::AlgebraClock::calls;
   out.host_algebra_max_dim = int(dense::AlgebraClock::max_dim);
+  if (refine_stats) {
+    refine_stats->refined_actions = solver.refined_actions();
+    refine_stats->first_refined_iteration = solver.first_refined_iteration();
+    refine_stats->max_delta = 0;
+    for (double d : solver.refine_delta()) refine_stats->max_delta = std::max(refine_stats->max_delta, d);
+  }
   const auto& st = solver.statistics();
   out.iterations = st.iterations;
   out.r_creations = st.r_creations;

@@ -430,6 +430,37 @@ class IterativeSolverTemplate {
   std::shared_ptr<Logger> logger() const { return m_logger; }
   subspace::XSpace<R, Q, P>& xspace() { return *m_xspace; }
 
+  // Refined mode, for a Q space stored in a narrower format than R (extension; off by default, and then
+  // every path is as it was).  Three things change, all in solve():
+  //  1. each new R parameter vector is rounded to the Q storage format (array::quantise_for_storage) before
+  //     problem.action sees it, so its copy into the Q space is exact and a_j = H q_j to the precision of R;
+  //  2. the new rows of H come from the stored Q parameters and the new actions in R's precision
+  //     (subspace.h XSpace::set_refined), so S and H are the exact projection onto span{q_j};
+  //  3. only the stored actions then carry error: for root i, |r_est - r_true| <= delta_i =
+  //     u sum_j |c_ji| |a_j| with u the unit roundoff of the storage (2^-24) and |a_j| kept on the host.
+  //     A root with est_i <= max(kappa delta_i, threshold + delta_i) -- its estimate is no longer accurate to
+  //     1 / kappa, or it could be declared converged on an unverified estimate -- gets its residual from
+  //     the action of its solution instead: one more action per such root and iteration, all refined roots
+  //     of a batch in one call -- converged roots included, since the solver recomputes every root's residual
+  //     in every iteration.  That is the price of actions stored in 4 bytes.
+  // Scope: the hermitian LinearEigensystemDavidson, no max_size_qspace, reset_D or reset_D_max_Q_size, an
+  // empty D space (each is an error naming the option), and solve() only: add_vector called by hand has no
+  // action to refine with and throws.
+  void set_refine(bool on, double kappa = 8.0) {
+    m_xspace->set_refined(on);
+    m_refine = on;
+    m_refine_kappa = kappa > 0 ? kappa : 8.0;
+    m_refined_actions = 0;
+    m_first_refined_iteration = 0;
+    m_refine_delta.clear();
+  }
+  bool refine() const { return m_refine; }
+  double refine_kappa() const { return m_refine_kappa; }
+  //! actions spent on refined residuals; the iteration (from 1) of the first; the last delta of each root
+  int refined_actions() const { return m_refined_actions; }
+  int first_refined_iteration() const { return m_first_refined_iteration; }
+  const std::vector<double>& refine_delta() const { return m_refine_delta; }
+
   //! The current settings (reference IterativeSolverTemplate.h:262-267; derived solvers add theirs).
   virtual std::shared_ptr<Options> get_options() const {
     auto o = std::make_shared<Options>();
@@ -452,6 +483,15 @@ class IterativeSolverTemplate {
              bool generate_initial_guess = false) {
     if (parameters.empty()) throw std::runtime_error("Empty container passed to IterativeSolver::solve()");
     if (parameters.size() != actions.size()) throw std::runtime_error("Inconsistent container sizes in IterativeSolver::solve()");
+    // refined mode: the solver reaches the problem's action for the refined residuals while solve() runs
+    struct HookScope {
+      action_hook_type& hook;
+      ~HookScope() { hook = nullptr; }
+    } hook_scope{m_action_hook};
+    if (m_refine) {
+      check_refine();
+      m_action_hook = [&problem](const CVecRef<R>& x, const VecRef<R>& a) { problem.action(x, a); };
+    }
     const bool use_diagonals = problem.diagonals(actions.at(0));
     std::unique_ptr<Q> diagonals;
     if (use_diagonals) diagonals = std::make_unique<Q>(m_handlers->qr().copy(actions.at(0)));
@@ -482,6 +522,10 @@ class IterativeSolverTemplate {
         const auto value = problem.residual(parameters.front(), actions.front());
         nwork = add_vector(parameters.front().get(), actions.front().get(), value);
       } else if (iter > 0 || pspace.empty()) {
+        if (m_refine) {  // the action must belong to the vector the Q space will hold
+          using array::quantise_for_storage;
+          quantise_for_storage(m_handlers->qr(), wrap(parameters.begin(), parameters.begin() + nwork));
+        }
         problem.action(cwrap(parameters.begin(), parameters.begin() + nwork), wrap(actions.begin(), actions.begin() + nwork));
         nwork = add_vector(parameters, actions);
       }
@@ -557,6 +601,7 @@ class IterativeSolverTemplate {
         detail::update_errors(errors, cwrap(action), m_handlers->rr());
       }
       m_residual_norms2.clear();
+      if (m_refine) refine_residuals(roots, parameters, action, errors);
       if (batches.size() > 1) {
         for (size_t i = 0; i < roots.size(); ++i)
           temp.emplace_back(m_handlers->qr().copy(parameters[i]), m_handlers->qr().copy(action[i]));
@@ -584,6 +629,60 @@ class IterativeSolverTemplate {
     return m_working_set.size();
   }
 
+  using action_hook_type = std::function<void(const CVecRef<R>&, const VecRef<R>&)>;
+
+  //! Throws unless this solver, as it is set up, supports the refined mode (set_refine).
+  virtual void check_refine() const {
+    throw std::logic_error("refine: available for the hermitian LinearEigensystemDavidson only");
+  }
+
+  // Step 3 of the refined mode (set_refine), after solution() has built the batch: the roots whose estimate
+  // the bound no longer vouches for get r = H x - lambda x from the action of the solution itself (the P
+  // space's part is inside H x: no apply_p), and their errors are recomputed.  The decision uses reduced
+  // quantities only (estimates, subspace coefficients, action norms), so every rank takes it alike.
+  void refine_residuals(const std::vector<int>& roots, const VecRef<R>& parameters, const VecRef<R>& action,
+                        std::vector<double>& errors) {
+    const auto& d = m_xspace->dimensions();
+    if (d.nQ == 0) return;  // nothing is stored rounded yet
+    if (d.nD != 0) throw std::runtime_error("refine: a D space is not supported");
+    if (!m_action_hook)
+      throw std::logic_error("refine: needs the problem's action, which only solve() provides (not add_vector by hand)");
+    check_refine();
+    const auto& norms = m_xspace->q_action_norms();
+    const auto& sol = m_subspace_solver->solutions();
+    constexpr double u = 5.9604644775390625e-08;  // 2^-24, the unit roundoff of binary32
+    if (m_refine_delta.size() < sol.rows()) m_refine_delta.resize(sol.rows(), 0.0);
+    std::vector<int> rroots;
+    VecRef<R> rx, ra;
+    std::vector<size_t> slot;
+    for (size_t i = 0; i < roots.size(); ++i) {
+      double delta = 0;
+      for (size_t j = 0; j < d.nQ; ++j) delta += std::abs(sol(size_t(roots[i]), d.oQ + j)) * norms.at(j);
+      delta *= u;
+      m_refine_delta[size_t(roots[i])] = delta;
+      if (errors[i] <= std::max(m_refine_kappa * delta, m_convergence_threshold + delta)) {
+        rroots.push_back(roots[i]);
+        rx.push_back(parameters[i]);
+        ra.push_back(action[i]);
+        slot.push_back(i);
+      }
+    }
+    if (rroots.empty()) return;
+    m_action_hook(cwrap(rx.begin(), rx.end()), ra);
+    m_refined_actions += int(rroots.size());
+    if (m_first_refined_iteration == 0) m_first_refined_iteration = m_stats->iterations + 1;
+    m_residual_norms2.clear();
+    construct_residual(rroots, cwrap(rx.begin(), rx.end()), ra);
+    std::vector<double> e(rroots.size(), 0);
+    if (m_residual_norms2.size() == rroots.size()) {
+      for (size_t i = 0; i < e.size(); ++i) e[i] = std::sqrt(std::abs(m_residual_norms2[i]));
+    } else {
+      detail::update_errors(e, cwrap(ra.begin(), ra.end()), m_handlers->rr());
+    }
+    m_residual_norms2.clear();
+    for (size_t i = 0; i < e.size(); ++i) errors[slot[i]] = e[i];
+  }
+
   void check_roots(const std::vector<int>& roots, size_t nparams) const {
     if (roots.size() > nparams) throw std::runtime_error("asking for more roots than parameters");
     if (!roots.empty() && size_t(*std::max_element(roots.begin(), roots.end())) >= m_subspace_solver->solutions().rows())
@@ -608,6 +707,13 @@ class IterativeSolverTemplate {
   size_t m_max_p = 0;
   double m_p_threshold = std::numeric_limits<double>::max();
   bool m_end_iteration_needed = true;
+  // refined mode (set_refine)
+  bool m_refine = false;
+  double m_refine_kappa = 8.0;
+  action_hook_type m_action_hook{};  // problem.action, set by solve() for its duration
+  int m_refined_actions = 0;
+  int m_first_refined_iteration = 0;  // 0: none yet
+  std::vector<double> m_refine_delta;
 };
 
 // ---- Davidson ----------------------------------------------------------------------------------
@@ -773,6 +879,17 @@ class LinearEigensystemDavidson : public DavidsonSolver<R, Q, P> {
   }
 
  protected:
+  // The refined mode's scope (IterativeSolverTemplate::set_refine): each limit is an error naming the option.
+  void check_refine() const override {
+    constexpr int unlimited = std::numeric_limits<int>::max();
+    if (!this->get_hermiticity()) throw std::runtime_error("refine: needs hermitian = 1 (hermiticity)");
+    if (this->get_max_size_qspace() != unlimited)
+      throw std::runtime_error("refine: max_size_qspace must be unlimited (a D space is not supported)");
+    if (this->get_reset_D() != unlimited) throw std::runtime_error("refine: reset_D must be off (a D space is not supported)");
+    if (this->get_reset_D_maxQ_size() != unlimited)
+      throw std::runtime_error("refine: reset_D_max_Q_size must be unlimited (a D space is not supported)");
+  }
+
   void set_value_errors() override {
     const auto cur = this->m_subspace_solver->eigenvalues();
     this->m_value_errors.assign(cur.size(), std::numeric_limits<double>::max());

@@ -12,6 +12,7 @@
 // Every vector operation goes through the ArrayHandlers bundle; the host only touches the small
 // matrices.
 #pragma once
+#include <cmath>
 #include <list>
 #include <map>
 #include <memory>
@@ -233,11 +234,29 @@ class XSpace {
     m_logger->msg("XSpace::update_qspace", Logger::Trace);
     auto nd = new_qspace_data(params, actions);
     qspace.update(params, actions, nd.qq, nd.qx, nd.xq, m_dim, data);
+    // the new vectors are prepended in their order (QSpace::update), their action norms with them
+    if (m_refined) m_q_action_norms.insert(m_q_action_norms.begin(), m_new_action_norms.begin(), m_new_action_norms.end());
     update_dimensions();
   }
 
+  // Refined mode (solvers.h, IterativeSolverTemplate::set_refine), for a Q space stored in a narrower
+  // format than R and new parameters that were rounded to that format BEFORE their action was computed:
+  // the new rows of H come from the stored Q parameters and the new full-precision actions, never from the
+  // stored (rounded) Q actions, so S and H are the projection onto the span of the stored parameters in the
+  // precision of R.  Hermitian, no D space.  |a_j| of every Q vector's action is kept beside the Q space
+  // (q_action_norms, Q order: newest first) for the solver's bound on the error of its residual.
+  void set_refined(bool on) {
+    if (on && m_dim.nQ + m_dim.nD != 0) throw std::logic_error("refine: must be set on an empty subspace");
+    m_refined = on;
+    m_q_action_norms.clear();
+  }
+  bool refined() const { return m_refined; }
+  const std::vector<double>& q_action_norms() const { return m_q_action_norms; }
+
   // Replaces the D space and recomputes its blocks of S and H (reference XSpace.h:174-187).
   void update_dspace(VecRef<Q>& params, VecRef<Q>& actions) {
+    if (m_refined && !params.empty())
+      throw std::runtime_error("refine: a D space is not supported (its stored pairs are rounded combinations)");
     dspace.update(params, actions);
     update_dimensions();
     for (auto e : {EqnData::H, EqnData::S}) data[e].resize({m_dim.nX, m_dim.nX});
@@ -307,6 +326,7 @@ class XSpace {
 
   void eraseq(size_t i) {
     qspace.erase(i);
+    if (m_refined) m_q_action_norms.erase(m_q_action_norms.begin() + long(i));
     remove_data(m_dim.oQ + i);
     update_dimensions();
   }
@@ -400,6 +420,7 @@ class XSpace {
         for (size_t j = 0; j < m_rhs.size(); ++j) qq[EqnData::rhs](i, j) = g(i, cR + j);
       }
     };
+    if (m_refined) m_new_action_norms.assign(nn, 0.0);  // (Q = R stores its actions exactly: no error to bound)
     if constexpr (std::is_same_v<R, Q>) {
       // every block whose rows are the new parameters, as one batched overlap where the handler has
       // it: columns [params, actions, Q params, Q actions, D params, D actions, rhs]
@@ -424,7 +445,40 @@ class XSpace {
       // two lists, where the R x Q handler has the batched form (array::fused_overlap_rows_mixed)
       Matrix<double> g;
       using array::fused_overlap_rows_mixed;
-      if (!m_action_dot_action && nn > 0 &&
+      if (m_refined) {
+        // rows [params, actions] against the f64 columns [params, actions] and the stored columns
+        // [Q params, rhs]: S(new, .) from the params rows, H(new, new) = params . actions, H(Q, new) from the
+        // actions rows against the Q params (the products of the non-hermitian branch below), and the
+        // diagonal actions . actions for the norms; the stored Q actions are not read
+        if (!m_hermitian || m_action_dot_action) throw std::logic_error("refine: hermitian kernels only");
+        if (d.nD != 0) throw std::runtime_error("refine: a D space is not supported");
+        CVecRef<R> rows(params.begin(), params.end());
+        rows.insert(rows.end(), actions.begin(), actions.end());
+        if (nn > 0 && fused_overlap_rows_mixed(h.rq(), rows, std::vector<CVecRef<R>>{params, actions},
+                                               std::vector<CVecRef<Q>>{qp, rhs()}, g)) {
+          const size_t cA = nn, cQ = 2 * nn, cR = cQ + d.nQ;
+          for (size_t i = 0; i < nn; ++i) {
+            for (size_t j = 0; j <= i; ++j) qq[EqnData::S](i, j) = qq[EqnData::S](j, i) = g(i, j);
+            for (size_t j = 0; j < nn; ++j) qq[EqnData::H](i, j) = g(i, cA + j);
+            for (size_t j = 0; j < d.nQ; ++j) {
+              qx[EqnData::S](i, d.oQ + j) = g(i, cQ + j);
+              qx[EqnData::H](i, d.oQ + j) = g(nn + i, cQ + j);
+            }
+            for (size_t j = 0; j < m_rhs.size(); ++j) qq[EqnData::rhs](i, j) = g(i, cR + j);
+            m_new_action_norms[i] = std::sqrt(std::abs(g(nn + i, cA + i)));
+          }
+        } else {
+          qq[EqnData::S] = util::overlap(params, h.rr());
+          qx[EqnData::S].slice({0, d.oQ}, {nn, d.oQ + d.nQ}) = util::overlap(params, qp, h.rq());
+          qq[EqnData::H] = util::overlap(params, actions, h.rr());
+          qx[EqnData::H].slice({0, d.oQ}, {nn, d.oQ + d.nQ}) = util::overlap(actions, qp, h.rq());
+          qq[EqnData::rhs] = util::overlap(params, rhs(), h.rq());
+          for (size_t i = 0; i < nn; ++i)
+            m_new_action_norms[i] = std::sqrt(std::abs(h.rr().dot(actions[i].get(), actions[i].get())));
+        }
+        fused = true;  // the blocks are in place either way
+      }
+      if (!m_refined && !m_action_dot_action && nn > 0 &&
           fused_overlap_rows_mixed(h.rq(), params, std::vector<CVecRef<R>>{params, actions},
                                    std::vector<CVecRef<Q>>{qp, qa, dp, da, rhs()}, g)) {
         fused = true;
@@ -502,6 +556,9 @@ class XSpace {
   std::vector<double> m_rhs_norm;
   bool m_hermitian = false;
   bool m_action_dot_action = false;
+  bool m_refined = false;
+  std::vector<double> m_q_action_norms;    // |a_j| per Q vector, Q order
+  std::vector<double> m_new_action_norms;  // the same of the vectors new_qspace_data was last called with
 };
 
 }  // namespace molpro::linalg::itsolv::subspace

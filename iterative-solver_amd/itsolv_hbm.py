@@ -22,9 +22,13 @@ EXPORTS = [
     "itsolv_davidson_synth", "itsolv_diis_synth",
     # Davidson with the Q space stored in f32 (itsolv_hbm/hbm_vec_f32.h)
     "itsolv_davidson_dense_q32", "itsolv_davidson_synth_q32",
+    # the same in the refined mode (f64 thresholds), and what the last refined solve spent
+    "itsolv_davidson_dense_q32_refined", "itsolv_davidson_synth_q32_refined", "itsolv_q32_refine_stats",
 ]
 # Absent from the CPU emulation of the library (loaded through this binding by patching LIB_PATH).
 OPTIONAL = frozenset(n for n in EXPORTS if n.endswith("_q32"))
+# The refined mode's entry points, optional in the same way; a set of their own: OPTIONAL stays the plain f32 Q space.
+OPTIONAL_REFINED = frozenset(n for n in EXPORTS if n.endswith("_q32_refined") or n == "itsolv_q32_refine_stats")
 
 # Diagonal families of the synthetic H (include/subspace_hip.h sspx_synth, itsolv_hbm/problems.h).
 DIAG_LINEAR, DIAG_BOUNDED = 0, 1
@@ -40,6 +44,11 @@ def c5_spec(n: int, rank: int = 1, seed: int = 3, alpha: float = 0.2) -> dict:
     H = diag(1 + 2 frac(g phi1)) + (1/n) sum_l u_l u_l^T, preconditioner diagonal mismatched by alpha,
     t = 1/sqrt(n) (a unit-norm solution).  Keyword arguments of diis_synthetic / oracle.diis_synthetic."""
     return dict(rho=1.0 / n, rank=rank, seed=seed, diag_kind=DIAG_BOUNDED, alpha=alpha, target=1.0 / math.sqrt(n))
+
+
+class Refine(C.Structure):
+    """itsolv_q32_refine: kappa <= 0 means the default of 8."""
+    _fields_ = [("kappa", C.c_double)]
 
 
 class Options(C.Structure):
@@ -138,6 +147,7 @@ def load_library():
         L = C.CDLL(LIB_PATH)
         P, Z, D, I, U = C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_ulonglong
         PO, PR, PD = C.POINTER(Options), C.POINTER(Result), C.POINTER(C.c_double)
+        PF, PI = C.POINTER(Refine), C.POINTER(C.c_int)
         sig = {
             "itsolv_last_error": (C.c_char_p, []),
             "itsolv_default_options": (None, [PO]),
@@ -151,9 +161,12 @@ def load_library():
             "itsolv_diis_synth": (I, [P, Z, C.POINTER(Synth), PO, PR, PD]),
             "itsolv_davidson_dense_q32": (I, [P, PD, Z, PO, PR, PD]),
             "itsolv_davidson_synth_q32": (I, [P, Z, C.POINTER(Synth), PO, PR, PD]),
+            "itsolv_davidson_dense_q32_refined": (I, [P, PD, Z, PO, PF, PR, PD]),
+            "itsolv_davidson_synth_q32_refined": (I, [P, Z, C.POINTER(Synth), PO, PF, PR, PD]),
+            "itsolv_q32_refine_stats": (I, [PI, PI, PD]),
         }
         for name, (res, args) in sig.items():
-            if name in OPTIONAL and not hasattr(L, name):
+            if (name in OPTIONAL or name in OPTIONAL_REFINED) and not hasattr(L, name):
                 continue
             f = getattr(L, name)
             f.restype = res
@@ -162,14 +175,33 @@ def load_library():
     return _lib
 
 
-def _entry(name: str, q32: bool):
-    """The solver entry point `name`, or with q32 its form over a Q space stored in f32."""
+def _entry(name: str, q32: bool, refine: bool = False):
+    """The solver entry point `name`, or with q32 its form over a Q space stored in f32 (refine: in the
+    refined mode)."""
+    if refine and not q32:
+        raise ValueError("refine=True needs q32=True: the refined mode is a mode of the f32 Q space")
     if not q32:
         return getattr(load_library(), name)
-    f = getattr(load_library(), name + "_q32", None)
+    full = name + ("_q32_refined" if refine else "_q32")
+    f = getattr(load_library(), full, None)
     if f is None:
-        raise sh.SspError(7, f"{name}_q32: the loaded library has no f32 Q space")
+        raise sh.SspError(7, f"{full}: the loaded library has no f32 Q space")
     return f
+
+
+def _refine_args(refine: bool, kappa):
+    """The extra argument of a *_q32_refined entry (none for the others)."""
+    if not refine:
+        if kappa is not None:
+            raise ValueError("kappa is an option of refine=True")
+        return ()
+    return (C.byref(Refine(0.0 if kappa is None else float(kappa))),)
+
+
+def _refine_stats() -> dict:
+    a, f, d = C.c_int(), C.c_int(), C.c_double()
+    load_library().itsolv_q32_refine_stats(C.byref(a), C.byref(f), C.byref(d))
+    return {"refined_actions": a.value, "first_refined_iteration": f.value, "max_delta": d.value}
 
 
 def _call(fn, args, nout):
@@ -185,25 +217,35 @@ def _call(fn, args, nout):
 
 def davidson_synthetic(ctx: sh.Context, n: int, rho: float, rank: int, seed: int, n_local: int | None = None,
                        solutions: bool = True, *, diag_kind: int = DIAG_LINEAR, alpha: float = 0.0,
-                       target: float = 1.0, q32: bool = False, **opts):
-    """q32: the Q space is stored in f32 (half the HBM and bytes of every pass over it; arithmetic in f64)."""
+                       target: float = 1.0, q32: bool = False, refine: bool = False, kappa: float | None = None,
+                       **opts):
+    """q32: the Q space is stored in f32 (half the HBM and bytes of every pass over it; arithmetic in f64).
+    refine (with q32): the refined mode, which reaches f64 thresholds at the price of one more action per
+    refined root and iteration (include/itsolv_hbm.h); the result then has "refine" (its statistics)."""
+    fn = _entry("itsolv_davidson_synth", q32, refine)
     o = make_options(**opts)
     nl = n if n_local is None else n_local
     spec = Synth(rho, rank, seed, diag_kind, alpha, target)
-    r, sol = _call(_entry("itsolv_davidson_synth", q32), (ctx.handle, n, C.byref(spec), C.byref(o)),
+    r, sol = _call(fn, (ctx.handle, n, C.byref(spec), C.byref(o)) + _refine_args(refine, kappa),
                    o.nroots * nl if solutions else 0)
+    if refine:
+        r["refine"] = _refine_stats()
     if solutions:
         r["solutions"] = sol[: o.nroots * nl].reshape(o.nroots, nl)
     return r
 
 
-def davidson_dense(ctx: sh.Context, h: np.ndarray, q32: bool = False, **opts):
-    """q32: the Q space is stored in f32 (arithmetic in f64)."""
+def davidson_dense(ctx: sh.Context, h: np.ndarray, q32: bool = False, refine: bool = False,
+                   kappa: float | None = None, **opts):
+    """q32: the Q space is stored in f32 (arithmetic in f64); refine: as davidson_synthetic's."""
+    fn = _entry("itsolv_davidson_dense", q32, refine)
     h = np.ascontiguousarray(h, dtype=np.float64)
     n = h.shape[0]
     o = make_options(**opts)
-    r, sol = _call(_entry("itsolv_davidson_dense", q32),
-                   (ctx.handle, h.ctypes.data_as(C.POINTER(C.c_double)), n, C.byref(o)), o.nroots * n)
+    r, sol = _call(fn, (ctx.handle, h.ctypes.data_as(C.POINTER(C.c_double)), n, C.byref(o))
+                   + _refine_args(refine, kappa), o.nroots * n)
+    if refine:
+        r["refine"] = _refine_stats()
     r["solutions"] = sol[: o.nroots * n].reshape(o.nroots, n)
     return r
 

@@ -54,12 +54,16 @@ EXPORTS = [
     "ssp_mx_copy", "ssp_mx_axpy", "ssp_mx_dot", "ssp_mx_gemm_inner", "ssp_mx_gemm_outer",
     # fused solver passes over an f32 Q space beside f64 R vectors
     "ssp_q32_gemm_inner_cols", "ssp_q32_construct_solution", "ssp_q32_block_update",
+    # the refined f32 Q space: f64 vectors rounded through f32 in place
+    "ssp_quantise_f32",
 ]
 
 # The mixed-precision entry points are optional in a loaded library: the CPU emulation of the f64 C ABI
 # (loaded through these bindings by patching LIB_PATH) does not have them, and a call then raises
 # SspError(SSP_ERR_UNSUPPORTED).
-OPTIONAL = frozenset(n for n in EXPORTS if n.endswith("_f32") or n.startswith("ssp_mx_"))
+# The entry points of the refined f32 Q space, optional in the same way and again a set of their own.
+OPTIONAL_REFINED = frozenset({"ssp_quantise_f32"})
+OPTIONAL = frozenset(n for n in EXPORTS if n.endswith("_f32") or n.startswith("ssp_mx_")) - OPTIONAL_REFINED
 # The fused passes over an f32 Q space are tolerated in the same way (absent from the emulation, a call
 # raises SspError(SSP_ERR_UNSUPPORTED)); they are a set of their own: OPTIONAL stays the storage layer.
 OPTIONAL_Q32 = frozenset(n for n in EXPORTS if n.startswith("ssp_q32_"))
@@ -188,12 +192,13 @@ def _declare(lib):
         "ssp_mx_dot": (I, [P, P, I, P, I, Z, PD]),
         "ssp_mx_gemm_inner": (I, [P, P, I, PD, I, P, I, PD, I, Z, PD]),
         "ssp_mx_gemm_outer": (I, [P, PD, P, I, PD, I, P, I, I, Z, I]),
+        "ssp_quantise_f32": (I, [P, P, PD, I, Z]),
         "ssp_q32_gemm_inner_cols": (I, [P, P, PD, I, P, C.POINTER(I), PD, I, Z, PD]),
         "ssp_q32_construct_solution": (I, [P, PD, PZ, PZ, PD, I, PD, P, I, P, I, Z, Z]),
         "ssp_q32_block_update": (I, [P, PD, PZ, PZ, PD, I, PD, P, I, P, PD, I, Z, Z]),
     }
     for name, (res, args) in sig.items():
-        if (name in OPTIONAL or name in OPTIONAL_Q32) and not hasattr(lib, name):
+        if (name in OPTIONAL or name in OPTIONAL_Q32 or name in OPTIONAL_REFINED) and not hasattr(lib, name):
             continue
         f = getattr(lib, name)
         f.restype = res
@@ -793,6 +798,15 @@ class Context:
     def mx_copy(self, x: DeviceVector, y: DeviceVector, ys: float = 1.0):
         """x = (x.dtype)(ys * y)"""
         _check(self._mx("ssp_mx_copy")(self.handle, x.ptr, _code(x), y.ptr, _code(y), float(ys), x.n))
+
+    def quantise_f32(self, vectors: Sequence[DeviceVector], xs=None):
+        """vectors[v] = float64(float32(xs[v] * vectors[v])) in place: float64 vectors rounded through f32."""
+        f = self._mx("ssp_quantise_f32")
+        if any(_code(v) != SSP_F64 for v in vectors):
+            raise TypeError("quantise_f32: the vectors are float64 vectors")
+        m = len(vectors)
+        a = self._scales(xs, m)
+        _check(f(self.handle, _ptrs(vectors), _dptr(a), m, vectors[0].n if m else 0))
 
     def mx_axpy(self, alpha: float, x: DeviceVector, y: DeviceVector):
         _check(self._mx("ssp_mx_axpy")(self.handle, float(alpha), x.ptr, _code(x), y.ptr, _code(y), y.n))

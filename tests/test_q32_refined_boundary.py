@@ -1,0 +1,157 @@
+"""The boundary of the refined f32 Q space (include/itsolv_hbm.h *_q32_refined, ssp_quantise_f32), checked
+without a GPU: the libraries export the new C ABI, the bindings declare it and keep loading a library that
+lacks it (the CPU emulation of the f64 ABI), the refined solver compiles for <Vec, VecF32, SparseP>, and
+the f64 headers still do not see the f32 ones."""
+import ctypes
+import os
+import subprocess
+import sys
+import tempfile
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "iterative-solver_amd")
+LIBDIR = os.path.join(PKG, "lib")
+EMUL = os.path.join(ROOT, "oracle", "build")
+
+SSP_NAMES = ["ssp_quantise_f32"]
+ITSOLV_NAMES = ["itsolv_davidson_dense_q32_refined", "itsolv_davidson_synth_q32_refined", "itsolv_q32_refine_stats"]
+
+
+def test_libraries_export_the_refined_abi():
+    so = ctypes.CDLL(os.path.join(LIBDIR, "libsubspace_hip.so"), mode=ctypes.RTLD_GLOBAL)
+    assert not [n for n in SSP_NAMES if not hasattr(so, n)]
+    it = ctypes.CDLL(os.path.join(LIBDIR, "libitsolv_hbm.so"))
+    assert not [n for n in ITSOLV_NAMES if not hasattr(it, n)]
+
+
+def test_bindings_list_and_declare_the_new_names():
+    """The new names are optional at load.  They are sets of their own (OPTIONAL_REFINED), as OPTIONAL_Q32 is:
+    OPTIONAL stays the set tests/test_mixed_boundary.py pins."""
+    import itsolv_hbm as ih
+    import subspace_hip as sh
+
+    assert set(SSP_NAMES) <= set(sh.EXPORTS) and set(SSP_NAMES) == set(sh.OPTIONAL_REFINED)
+    assert set(ITSOLV_NAMES) <= set(ih.EXPORTS) and set(ITSOLV_NAMES) == set(ih.OPTIONAL_REFINED)
+    assert not set(SSP_NAMES) & (set(sh.OPTIONAL) | set(sh.OPTIONAL_Q32)) and not set(ITSOLV_NAMES) & set(ih.OPTIONAL)
+    assert len(sh.load_library().ssp_quantise_f32.argtypes) == 5
+    lib = ih.load_library()
+    assert len(lib.itsolv_davidson_dense_q32_refined.argtypes) == 7
+    assert len(lib.itsolv_davidson_synth_q32_refined.argtypes) == 7
+    assert len(lib.itsolv_q32_refine_stats.argtypes) == 3
+    assert ctypes.sizeof(ih.Refine) == 8
+    # the stats call works without a device: nothing has run on this thread
+    assert ih._refine_stats() == {"refined_actions": 0, "first_refined_iteration": 0, "max_delta": 0.0}
+    with pytest.raises(ValueError, match="refine.*q32"):
+        ih._entry("itsolv_davidson_dense", False, True)
+    with pytest.raises(ValueError, match="kappa"):
+        ih._refine_args(False, 4.0)
+
+
+EMUL_SCRIPT = r"""
+import os, sys
+ROOT = sys.argv[1]
+for p in (ROOT, os.path.join(ROOT, "iterative-solver_amd"), os.path.join(ROOT, "oracle")):
+    sys.path.insert(0, p)
+import numpy as np
+import itsolv_hbm as ih
+import subspace_hip as sh
+EMUL = os.path.join(ROOT, "oracle", "build")
+sh.LIB_PATH = os.path.join(EMUL, "libssp_emul.so")
+ih.LIB_PATH = os.path.join(EMUL, "libitsolv_emul.so")
+lib = sh.load_library()
+assert not hasattr(lib, "ssp_quantise_f32"), "the emulation is not expected to have the mixed entry points"
+assert not hasattr(ih.load_library(), "itsolv_davidson_dense_q32_refined")
+with sh.Context(0) as ctx:
+    x = ctx.upload(np.arange(5.0))
+    calls = [lambda: ctx.quantise_f32([x]),
+             lambda: ih.davidson_dense(ctx, np.eye(4), q32=True, refine=True, nroots=1),
+             lambda: ih.davidson_synthetic(ctx, 64, 0.1, 1, 1, q32=True, refine=True, kappa=4.0)]
+    for i, f in enumerate(calls):
+        try:
+            f()
+        except sh.SspError as e:
+            assert e.code == 7, (i, e)
+        else:
+            raise AssertionError(f"call {i} did not raise")
+    try:
+        ih.davidson_dense(ctx, np.eye(4), refine=True, nroots=1)
+    except ValueError as e:
+        assert "q32" in str(e)
+    else:
+        raise AssertionError("refine without q32 did not raise")
+    r = ih.davidson_dense(ctx, np.diag(np.arange(1.0, 9.0)), nroots=1, convergence_threshold=1e-8)
+    assert r["converged"] and abs(r["eigenvalues"][0] - 1.0) < 1e-8 and "refine" not in r
+print("ok")
+"""
+
+
+@pytest.mark.skipif(not os.path.exists(os.path.join(EMUL, "libssp_emul.so")), reason="needs `make -C oracle`")
+def test_bindings_load_a_library_without_the_refined_entry_points():
+    r = subprocess.run([sys.executable, "-c", EMUL_SCRIPT, ROOT], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-4000:]
+
+
+TU = r"""
+#include "itsolv_hbm/hbm_handlers_f32.h"
+#include "itsolv_hbm/problems.h"
+#include "itsolv_hbm/solvers.h"
+using namespace molpro::linalg;
+template class itsolv::LinearEigensystemDavidson<hbm::Vec, hbm::VecF32, hbm::SparseP>;
+using Solver = itsolv::LinearEigensystemDavidson<hbm::Vec, hbm::VecF32, hbm::SparseP>;
+// the hook resolves to the f32 overload for the Q x R handler of this pair, and to the default for Q = R
+bool quantise(itsolv::ArrayHandlers<hbm::Vec, hbm::VecF32, hbm::SparseP>& h, const itsolv::VecRef<hbm::Vec>& x) {
+  using array::quantise_for_storage;
+  return quantise_for_storage(h.qr(), x);
+}
+bool quantise_f64(itsolv::ArrayHandlers<hbm::Vec, hbm::Vec, hbm::SparseP>& h, const itsolv::VecRef<hbm::Vec>& x) {
+  using array::quantise_for_storage;
+  return quantise_for_storage(h.qr(), x);
+}
+bool solve(const itsolv::Problem<hbm::Vec, hbm::SparseP>& problem, std::vector<hbm::Vec>& x, std::vector<hbm::Vec>& a) {
+  Solver solver(hbm::make_handlers_q32());
+  solver.set_refine(true, 4.0);
+  const bool ok = solver.solve(x, a, problem, true);
+  return ok && solver.refined_actions() >= 0 && solver.first_refined_iteration() >= 0 && solver.refine_delta().empty();
+}
+void run(const itsolv::Problem<hbm::Vec, hbm::SparseP>& problem, const itsolv_options& o, itsolv_result& out) {
+  const double kappa = 0;
+  itsolv::problems::RefineStats stats;
+  itsolv::problems::run_davidson<hbm::Vec, hbm::VecF32, hbm::SparseP>(hbm::make_handlers_q32(), problem, {}, {}, o, out,
+                                                                     {}, {}, &kappa, &stats);
+}
+"""
+
+
+def makefile_cxxflags():
+    out = subprocess.run(["make", "-pn", "-C", PKG, "clean"], capture_output=True, text=True, timeout=120).stdout
+    for line in out.splitlines():
+        if line.startswith("CXXFLAGS := ") or line.startswith("CXXFLAGS = "):
+            return line.split("=", 1)[1].split()
+    raise AssertionError("CXXFLAGS not found in the Makefile's database")
+
+
+def test_refined_davidson_compiles_with_an_f32_q_space():
+    flags = makefile_cxxflags()
+    assert "-std=c++17" in flags
+    with tempfile.TemporaryDirectory() as d:
+        src = os.path.join(d, "q32_refined_tu.cpp")
+        with open(src, "w") as f:
+            f.write(TU)
+        r = subprocess.run([os.environ.get("CXX", "g++")] + flags + ["-fsyntax-only", src], cwd=PKG, capture_output=True,
+                           text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-6000:]
+
+
+def test_f64_headers_do_not_see_the_f32_ones():
+    inc = os.path.join(PKG, "include", "itsolv_hbm")
+    for name in os.listdir(inc):
+        if name in ("hbm_vec_f32.h", "hbm_handlers_f32.h"):
+            continue
+        text = open(os.path.join(inc, name)).read()
+        assert "hbm_vec_f32.h" not in text and "hbm_handlers_f32.h" not in text, name
+        assert "ssp_quantise" not in text and "ssp_mx_" not in text, name  # the hook is type-generic
+    for name in os.listdir(os.path.join(PKG, "host")):  # host/ is also built against the f64 emulation
+        text = open(os.path.join(PKG, "host", name)).read()
+        assert "ssp_mx_" not in text and "_f32" not in text and "ssp_quantise" not in text, name

@@ -4,7 +4,11 @@ ledger enabled and report, per handler operation, calls, kernel time, algorithmi
 plus the solve's wall time.  Complements bench.py (a fixed subspace-update step) with the op mix
 of real Davidson / DIIS iterations.
 
-usage: python tools/solver_ledger.py [--configs C2,C2-mgs,C3,C3-mgs,C5,C4-shard] [--q32] [--out profiles/r1/solver_ledger.json]
+usage: python tools/solver_ledger.py [--configs C2,C2-mgs,C3,C3-mgs,C5,C4-shard] [--q32] [--refine] [--no-q-limit]
+                                     [--threshold T] [--out profiles/r1/solver_ledger.json]
+--refine: the Davidson configs on the refined f32 Q space (include/itsolv_hbm.h *_q32_refined); its scope has no
+Q-space limit and no D space, so max_size_qspace and reset_D are dropped from the config.  --no-q-limit drops
+them for the other modes too (the like-for-like baselines); --threshold overrides convergence_threshold.
 """
 import argparse
 import json
@@ -43,6 +47,9 @@ REDUCING = ("dot", "gemm_inner", "axpy_inner", "scal_inner", "axpy_norm", "axpy_
             # a Q space stored in f32 (--q32)
             "dot_f32", "gemm_inner_f32", "gemm_inner_cols")
 Q32 = False  # --q32: the Davidson configs with the Q space stored in f32
+REFINE = False  # --refine: ... in the refined mode
+NO_Q_LIMIT = False  # --no-q-limit
+THRESHOLD = None  # --threshold
 
 
 def run(ctx, name, repeat=2):
@@ -53,8 +60,8 @@ def run(ctx, name, repeat=2):
         cold = run_once(ctx, name)["wall_s"]
     out = run_once(ctx, name)
     out["wall_s_cold"] = cold
-    print(json.dumps({k: out[k] for k in ("config", "iterations", "wall_s", "wall_s_cold", "kernel_ms", "kernel_GBs", "reductions_per_iteration", "host_overhead_ms", "host_algebra",
-                                            "wall_GBs")}), flush=True)
+    print(json.dumps({k: out[k] for k in ("config", "converged", "iterations", "wall_s", "wall_s_cold", "kernel_ms", "kernel_GBs", "reductions_per_iteration", "host_overhead_ms", "host_algebra",
+                                            "wall_GBs", "refine") if k in out}), flush=True)
     return out
 
 
@@ -62,11 +69,16 @@ def run_once(ctx, name):
     solver, n, kw = CONFIGS[name]
     kw = dict(kw)
     rho, rank, seed = kw.pop("rho"), kw.pop("rank"), kw.pop("seed")
+    if solver == "davidson" and (REFINE or NO_Q_LIMIT):
+        for k in ("max_size_qspace", "reset_D", "reset_D_max_Q_size"):
+            kw.pop(k, None)
+    if THRESHOLD is not None:
+        kw["convergence_threshold"] = THRESHOLD
     ctx.ledger_reset()
     ctx.ledger_enable(True)
     t0 = time.perf_counter()
     if solver == "davidson":
-        r = ih.davidson_synthetic(ctx, n, rho, rank, seed, n_local=0, q32=Q32, **kw)
+        r = ih.davidson_synthetic(ctx, n, rho, rank, seed, n_local=0, q32=Q32 or REFINE, refine=REFINE, **kw)
     else:
         r = ih.diis_synthetic(ctx, n, rho, rank, seed, n_local=0, **kw)
     wall = time.perf_counter() - t0
@@ -78,7 +90,8 @@ def run_once(ctx, name):
                 "GBs": round(v["bytes"] / (v["ms"] / 1e3) / 1e9, 1) if v["ms"] > 0 else None,
                 "share_of_kernel_time": round(v["ms"] / ms, 4) if ms else None}
            for op, v in sorted(led.items(), key=lambda kv: -kv[1]["ms"])}
-    out = {"config": name + ("-q32" if Q32 and solver == "davidson" else ""), "solver": solver, "n": n, "options": CONFIGS[name][2], "converged": r["converged"],
+    tag = ("-q32-refined" if REFINE else "-q32" if Q32 else "") if solver == "davidson" else ""
+    out = {"config": name + tag, "solver": solver, "n": n, "options": kw, "converged": r["converged"],
            "iterations": r["iterations"], "wall_s": round(wall, 3), "kernel_ms": round(ms, 3),
            "algorithmic_GB": round(nb / 1e9, 3), "kernel_GBs": round(nb / (ms / 1e3) / 1e9, 1) if ms else None,
            "wall_GBs": round(nb / wall / 1e9, 1), "ops": ops,
@@ -90,6 +103,10 @@ def run_once(ctx, name):
                             "max_dim": r["host_algebra"]["max_dim"]}}
     if solver == "davidson":
         out["eigenvalues"] = [float(e) for e in r["eigenvalues"]]
+        out["errors"] = [float(e) for e in r["errors"]]
+        out["residual_norms"] = [float(e) for e in r["residual_norms"]]
+    if "refine" in r:
+        out["refine"] = r["refine"]
     return out
 
 
@@ -100,9 +117,12 @@ def main():
     ap.add_argument("--rccl", action="store_true", help="attach a one-rank RCCL communicator (multi-rank path)")
     ap.add_argument("--p2p", action="store_true", help="attach a one-rank peer-memory communicator (multi-rank path)")
     ap.add_argument("--q32", action="store_true", help="Davidson configs with the Q space stored in f32")
+    ap.add_argument("--refine", action="store_true", help="... in the refined mode (drops the configs' Q-space limits)")
+    ap.add_argument("--no-q-limit", action="store_true", help="drop max_size_qspace / reset_D from the Davidson configs")
+    ap.add_argument("--threshold", type=float, default=None, help="override convergence_threshold")
     a = ap.parse_args()
-    global Q32
-    Q32 = a.q32
+    global Q32, REFINE, NO_Q_LIMIT, THRESHOLD
+    Q32, REFINE, NO_Q_LIMIT, THRESHOLD = a.q32, a.refine, a.no_q_limit, a.threshold
     ctx = sh.Context(0)
     if a.rccl:
         ctx.attach_comm(1, 0, sh.Context.unique_id())
