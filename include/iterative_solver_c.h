@@ -136,6 +136,37 @@ int IterativeSolverHbmMpiAttach(ssp_ctx* ctx, int64_t fcomm, const char* transpo
  * IterativeSolverErrors / IterativeSolverEigenvalues fill (used by the Fortran module). */
 size_t IterativeSolverHbmNRoots(void);
 
+/* ---- extension: R vectors in device memory ------------------------------------------------
+ * The device forms of the calls that stage R.  Each does exactly what its host twin does between
+ * copying the caller's arrays in and copying them out again -- the same solver call on the same
+ * staging vectors, including the non-linear branch of IterativeSolverAddVector -- with the two
+ * PCIe copies replaced by one device-to-device pass each (ssp_rows_import / ssp_rows_export,
+ * include/subspace_hip.h; a vector's pending normalisation scale is applied by the export itself).
+ *  - The pointers are DEVICE memory on the instance's device and hold THIS RANK'S SHARD only: row k
+ *    is [p + k*ld, p + k*ld + local), local = range_end - range_begin as returned by *Initialize,
+ *    ld >= local.  Any double* base and any ld are accepted (rows at 8 mod 16 move with 8-byte
+ *    accesses); an even ld over a 16-byte aligned base is the fast path.  The calls without an ld
+ *    (AddValue, SetDiagonals, Diagonals) move one row.  The block must not overlap the library's own
+ *    vectors.
+ *  - There is no `sync` argument: gathering a working set into global arrays on every rank is a notion
+ *    of host arrays.
+ *  - Stream contract: the work is enqueued on the instance's context stream (ssp_ctx_stream).  Whatever
+ *    produces the inputs must be ordered on that stream, or finished, before the call; on return the
+ *    outputs are ordered on that stream (a consumer on it needs no synchronisation, any other consumer
+ *    ssp_synchronize).  The scalar results (return values, Errors, Eigenvalues) are host values as before.
+ *  - Host and device forms may be mixed call by call on one instance: both only stage.  This is how a P
+ *    space enters -- IterativeSolverAddP stays host-only, device calls follow it.
+ *  - Out of scope: a device-side apply_on_p callback, and the Fortran module (it binds the host forms).
+ *  - Errors as for the host forms; a library vector layer without the row-block entry points (the CPU
+ *    emulation used by the tests) moves 16-byte aligned rows one by one and refuses a misaligned row
+ *    before anything has been staged. */
+size_t IterativeSolverHbmAddVectorDevice(size_t buffer_size, double* parameters, double* action, size_t ld);
+void IterativeSolverHbmSolutionDevice(int nroot, int* roots, double* parameters, double* action, size_t ld);
+size_t IterativeSolverHbmAddValueDevice(double value, double* parameters, double* action);
+size_t IterativeSolverHbmEndIterationDevice(size_t buffer_size, double* solution, double* residual, size_t ld);
+void IterativeSolverHbmSetDiagonalsDevice(const double* diagonals);
+void IterativeSolverHbmDiagonalsDevice(double* diagonals);
+
 #ifdef __cplusplus
 }
 #endif

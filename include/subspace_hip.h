@@ -271,6 +271,30 @@ int ssp_block_update(ssp_ctx* ctx, const double* palphas, const size_t* ptr, con
                      int kp, const double* alphas, const double* const* xx, const double* xs, int k, double* const* yy,
                      const double* ys, int m, size_t n, size_t offset);
 
+/* ---- row blocks: a caller's row-major block of m vectors (row k at block + k*ld, any double* base and
+ *      any ld >= n) into and out of library vectors, device to device, in one pass on the context's
+ *      stream (csrc/kernels_rows.hip; the device forms of the reverse-communication API,
+ *      include/iterative_solver_c.h, stage R through them).
+ *        - The library vectors (dst[k] of the import, src[k] of the export) are 16-byte aligned like every
+ *          other vector argument.  The caller's block need only be 8-byte aligned: this is the one place
+ *          where the library meets memory it did not allocate, so a row may sit at 8 mod 16 (an odd ld or
+ *          an odd base; with an odd ld the rows alternate).  Parity is decided per row: an aligned row
+ *          moves with the 16-byte accesses of ssp_copy (window shape and nontemporal accesses from 2^24
+ *          elements), a misaligned row with 8-byte accesses on both sides, lane by lane contiguous.
+ *        - The import is a bit copy.  The export of a row with xs[k] == 1 (xs NULL: every row) is a bit
+ *          copy; otherwise it stores the single product src[k][i] * xs[k], bit for bit ssp_scal followed
+ *          by a copy (a vector's deferred scale costs no pass of its own).
+ *        - Up to 16 rows go in one launch; more rows are chunked.  m = 0 or n = 0 does nothing; m < 0,
+ *          ld < n, a null pointer or a misaligned library vector is SSP_ERR_ARG.
+ *        - Deferred zero fills: the import's destinations are written in full (their fills are dropped),
+ *          a fill recorded for a source of either call is stored first.
+ *        - The caller's block must not overlap a library vector of the call (not checked).
+ *      Ledger names rows_import / rows_export, 16 bytes per element and row, one entry per launch. */
+/* dst[k][i] = src[k*ld + i],          k < m, i < n */
+int ssp_rows_import(ssp_ctx* ctx, const double* src, size_t ld, double* const* dst, int m, size_t n);
+/* dst[k*ld + i] = xs[k] * src[k][i],  xs NULL = all 1 */
+int ssp_rows_export(ssp_ctx* ctx, const double* const* src, const double* xs, int m, double* dst, size_t ld, size_t n);
+
 /* ---- mixed precision: vectors STORED in binary32, all arithmetic in FP64 (csrc/kernels_mixed.hip).
  *      The Q space of a solve is written once and afterwards only read; held in f32 it takes half
  *      the HBM and half the bytes of every pass over it (itsolv_hbm/hbm_vec_f32.h).  One rule: an f32

@@ -34,8 +34,8 @@ __device__ __forceinline__ double sc1(double v, double s) {
 }
 
 // Window shape: a wave covers kWinU x 64 consecutive double2 (kWinU KiB) of each vector per visit.
-constexpr int kWinU = 8;
-constexpr size_t kWinMin = size_t(1) << 24;  // elementwise ops switch to windows from 128 MiB vectors
+using ssp::kWinMin;
+using ssp::kWinU;
 constexpr int kDotU = 4;
 
 

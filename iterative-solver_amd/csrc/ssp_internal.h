@@ -143,6 +143,10 @@ constexpr int kOuterDst = 16;      // destinations per gemm_outer launch
 constexpr int kOuterAlpha = 384;   // alphas carried in the kernel argument block
 constexpr int kPrecVec = 16;       // vectors per precondition launch
 constexpr int kSelectTile = 2048;  // candidates sorted per workgroup in select
+// Window shape of the elementwise streaming kernels (kernels_stream.hip, kernels_rows.hip): a wave covers
+// kWinU x 64 consecutive double2 (kWinU KiB) of each vector per visit.
+constexpr int kWinU = 8;
+constexpr size_t kWinMin = size_t(1) << 24;  // elementwise ops switch to windows from 128 MiB vectors
 
 int set_error(int code, const std::string& msg);
 int hip_error(hipError_t e, const char* what);

@@ -27,7 +27,16 @@ using molpro::linalg::hbm::SparseP;
 using molpro::linalg::hbm::Vec;
 namespace it = molpro::linalg::itsolv;
 
+// Weak references (null when the loaded vector library lacks them): see import_rows below.
+extern "C" {
+int ssp_rows_import(ssp_ctx*, const double*, size_t, double* const*, int, size_t) __attribute__((weak));
+int ssp_rows_export(ssp_ctx*, const double* const*, const double*, int, double*, size_t, size_t) __attribute__((weak));
+}
+
 namespace {
+
+const auto rows_import_fn = &ssp_rows_import;
+const auto rows_export_fn = &ssp_rows_export;
 
 using Solver = it::IterativeSolverTemplate<Vec, Vec, SparseP>;
 using Davidson = it::LinearEigensystemDavidson<Vec, Vec, SparseP>;
@@ -142,6 +151,56 @@ void download(Instance& in, std::vector<Vec>& v, size_t nvec, double* host) {
     check(ssp_download(in.dev->ctx(), host + k * in.dimension + in.offset, v[k].data(), in.local), "ssp_download");
 }
 
+// Device rows [dev + k*ld, +local) <-> HBM staging, one pass each way (the device forms below).  The
+// row-block entry points are referenced weakly: this file is also linked against the CPU emulation of
+// the f64 C ABI, which has none, and then (or over an older library) the rows move one by one --
+// ssp_copy for a 16-byte aligned row, ssp_scal_copy where a scale is pending -- and a misaligned row is
+// refused, before anything is staged.
+void check_rows(const Instance& in, size_t nvec, const double* dev, size_t ld, bool have_kernel, const char* what) {
+  if (nvec == 0 || in.local == 0) return;
+  if (!dev) throw std::invalid_argument(std::string(what) + ": null device pointer");
+  if (ld < in.local) throw std::invalid_argument(std::string(what) + ": ld smaller than this rank's range");
+  if (have_kernel) return;
+  for (size_t k = 0; k < nvec; ++k)
+    if (reinterpret_cast<uintptr_t>(dev + k * ld) % 16 != 0)
+      throw std::logic_error(std::string(what) + ": SSP_ERR_UNSUPPORTED: row " + std::to_string(k) +
+                             " is not 16-byte aligned and the loaded library has no ssp_rows_import / "
+                             "ssp_rows_export");
+}
+void import_rows(Instance& in, std::vector<Vec>& v, size_t nvec, const double* dev, size_t ld) {
+  if (nvec == 0 || in.local == 0) return;
+  std::vector<double*> dst(nvec);
+  for (size_t k = 0; k < nvec; ++k) dst[k] = v[k].data_wo();
+  if (rows_import_fn) {
+    check(rows_import_fn(in.dev->ctx(), dev, ld, dst.data(), int(nvec), in.local), "ssp_rows_import");
+    return;
+  }
+  for (size_t k = 0; k < nvec; ++k) check(ssp_copy(in.dev->ctx(), dst[k], dev + k * ld, in.local), "ssp_copy");
+}
+void export_rows(Instance& in, const std::vector<Vec>& v, size_t nvec, double* dev, size_t ld) {
+  if (nvec == 0 || in.local == 0) return;
+  std::vector<const double*> src(nvec);
+  std::vector<double> xs(nvec);
+  for (size_t k = 0; k < nvec; ++k) {
+    src[k] = v[k].data_deferred();
+    xs[k] = v[k].scale();
+  }
+  if (rows_export_fn) {
+    check(rows_export_fn(in.dev->ctx(), src.data(), xs.data(), int(nvec), dev, ld, in.local), "ssp_rows_export");
+    return;
+  }
+  for (size_t k = 0; k < nvec; ++k) {
+    if (xs[k] == 1.0) check(ssp_copy(in.dev->ctx(), dev + k * ld, src[k], in.local), "ssp_copy");
+    else check(ssp_scal_copy(in.dev->ctx(), xs[k], dev + k * ld, src[k], in.local), "ssp_scal_copy");
+  }
+}
+// Both arrays of a device call, checked before either is staged.
+void check_pair(const Instance& in, size_t nvec, const double* a, const double* b, size_t ld, const char* what) {
+  const bool have = rows_import_fn && rows_export_fn;
+  check_rows(in, nvec, a, ld, have, what);
+  check_rows(in, nvec, b, ld, have, what);
+}
+
 // reference DistrArraySynchronize / gather_all (IterativeSolverCMPI.cpp:133-139): every rank
 // receives every rank's range of each vector.
 void synchronize(Instance& in, size_t nvec, double* host) {
@@ -162,6 +221,17 @@ void synchronize(Instance& in, size_t nvec, double* host) {
 }
 
 it::VecRef<Vec> first(std::vector<Vec>& v, size_t n) { return it::wrap(v.begin(), v.begin() + long(n)); }
+
+// add_vector on the staged R vectors (IterativeSolverAddVector and its device form).
+// Non-linear solvers take one vector through their own add_vector (for DIIS: the residual norm,
+// the convergence flag and the least-important-vector deletion, NonLinearEquationsDIIS.h:83-102),
+// as IterativeSolverTemplate::solve does for them (:379-382).  The reference's C layer reaches
+// the generic vector-list overload instead, which skips that logic.
+size_t add_vector_staged(Instance& in, size_t buffer_size) {
+  return in.solver->nonlinear() && buffer_size >= 1
+             ? size_t(in.solver->add_vector(in.rp[0], in.ra[0], 0.0))
+             : size_t(in.solver->add_vector(first(in.rp, buffer_size), first(in.ra, buffer_size)));
+}
 
 it::Verbosity verbosity_of(int v) {
   return v <= 0 ? it::Verbosity::None : v == 1 ? it::Verbosity::Summary : v == 2 ? it::Verbosity::Iteration
@@ -329,13 +399,7 @@ size_t IterativeSolverAddVector(size_t buffer_size, double* parameters, double* 
     ensure_r(in, buffer_size);
     upload(in, in.rp, buffer_size, parameters);
     upload(in, in.ra, buffer_size, action);
-    // Non-linear solvers take one vector through their own add_vector (for DIIS: the residual norm,
-    // the convergence flag and the least-important-vector deletion, NonLinearEquationsDIIS.h:83-102),
-    // as IterativeSolverTemplate::solve does for them (:379-382).  The reference's C layer reaches
-    // the generic vector-list overload instead, which skips that logic.
-    const size_t nwork = in.solver->nonlinear() && buffer_size >= 1
-                             ? size_t(in.solver->add_vector(in.rp[0], in.ra[0], 0.0))
-                             : size_t(in.solver->add_vector(first(in.rp, buffer_size), first(in.ra, buffer_size)));
+    const size_t nwork = add_vector_staged(in, buffer_size);
     // The reference's R vectors are views of these host arrays, so every vector the solver wrote
     // (solutions and residuals of all roots, batch by batch) reaches the caller; sync gathers the
     // working set (IterativeSolverCMPI.cpp:302-306).
@@ -452,6 +516,84 @@ size_t IterativeSolverAddP(size_t buffer_size, size_t nP, const size_t* offsets,
       synchronize(in, std::min(nwork, buffer_size), action);
     }
     return nwork;
+  });
+}
+
+// ---- R vectors in device memory (include/iterative_solver_c.h): each call is its host twin with the
+// upload / download pairs replaced by import_rows / export_rows on this rank's shard.
+size_t IterativeSolverHbmAddVectorDevice(size_t buffer_size, double* parameters, double* action, size_t ld) {
+  return guarded([&] {
+    auto& in = top();
+    check_pair(in, buffer_size, parameters, action, ld, "IterativeSolverHbmAddVectorDevice");
+    ensure_r(in, buffer_size);
+    import_rows(in, in.rp, buffer_size, parameters, ld);
+    import_rows(in, in.ra, buffer_size, action, ld);
+    const size_t nwork = add_vector_staged(in, buffer_size);
+    export_rows(in, in.rp, buffer_size, parameters, ld);
+    export_rows(in, in.ra, buffer_size, action, ld);
+    return nwork;
+  });
+}
+
+void IterativeSolverHbmSolutionDevice(int nroot, int* roots, double* parameters, double* action, size_t ld) {
+  guarded([&] {
+    auto& in = top();
+    const size_t n = size_t(nroot);
+    check_pair(in, n, parameters, action, ld, "IterativeSolverHbmSolutionDevice");
+    ensure_r(in, n);
+    std::vector<int> r(roots, roots + nroot);
+    in.solver->solution(r, first(in.rp, n), first(in.ra, n));
+    export_rows(in, in.rp, n, parameters, ld);
+    export_rows(in, in.ra, n, action, ld);
+  });
+}
+
+size_t IterativeSolverHbmAddValueDevice(double value, double* parameters, double* action) {
+  return guarded([&]() -> size_t {
+    auto& in = top();
+    check_pair(in, 1, parameters, action, in.local, "IterativeSolverHbmAddValueDevice");
+    ensure_r(in, 1);
+    import_rows(in, in.rp, 1, parameters, in.local);
+    import_rows(in, in.ra, 1, action, in.local);
+    const int r = in.solver->add_vector(in.rp[0], in.ra[0], value);
+    export_rows(in, in.rp, 1, parameters, in.local);
+    export_rows(in, in.ra, 1, action, in.local);
+    return r > 0 ? 1 : 0;
+  });
+}
+
+size_t IterativeSolverHbmEndIterationDevice(size_t buffer_size, double* solution, double* residual, size_t ld) {
+  return guarded([&] {
+    auto& in = top();
+    check_pair(in, buffer_size, solution, residual, ld, "IterativeSolverHbmEndIterationDevice");
+    ensure_r(in, buffer_size);
+    import_rows(in, in.rp, buffer_size, solution, ld);
+    import_rows(in, in.ra, buffer_size, residual, ld);
+    const size_t result = in.solver->end_iteration(first(in.rp, buffer_size), first(in.ra, buffer_size));
+    export_rows(in, in.rp, buffer_size, solution, ld);
+    export_rows(in, in.ra, buffer_size, residual, ld);
+    return result;
+  });
+}
+
+void IterativeSolverHbmSetDiagonalsDevice(const double* diagonals) {
+  guarded([&] {
+    auto& in = top();
+    check_rows(in, 1, diagonals, in.local, rows_import_fn != nullptr, "IterativeSolverHbmSetDiagonalsDevice");
+    std::vector<Vec> d;
+    d.emplace_back(in.dev, in.dimension);
+    import_rows(in, d, 1, diagonals, in.local);
+    in.diagonals = std::make_unique<Vec>(std::move(d[0]));
+  });
+}
+
+void IterativeSolverHbmDiagonalsDevice(double* diagonals) {
+  guarded([&] {
+    auto& in = top();
+    if (!in.diagonals) throw std::runtime_error("IterativeSolverHbmDiagonalsDevice: no diagonals set");
+    check_rows(in, 1, diagonals, in.local, rows_export_fn != nullptr, "IterativeSolverHbmDiagonalsDevice");
+    std::vector<Vec> d{*in.diagonals};  // shares the storage
+    export_rows(in, d, 1, diagonals, in.local);
   });
 }
 

@@ -2,7 +2,8 @@
 extension over src/molpro/linalg/IterativeSolverC.h) as a ctypes binding of the same C API in
 libitsolv_hbm.so (include/iterative_solver_c.h).  Class names, constructor arguments and methods
 follow the reference (iterative_solver_extension.pyx); the Q space and all subspace operations
-live in HBM, the parameter/residual arrays the caller passes stay numpy arrays.
+live in HBM, the parameter/residual arrays the caller passes stay numpy arrays -- or, for a caller whose
+action runs on the GPU, subspace_hip.DeviceRows (device memory: the IterativeSolverHbm*Device calls).
 
 Available: LinearEigensystem and LinearEquations (Davidson), NonLinearEquations (DIIS), Optimize
 (BFGS, SD).
@@ -26,6 +27,17 @@ _lib = None
 P, D, Z, I = C.c_void_p, C.c_double, C.c_size_t, C.c_int
 PD, PZ, PI = C.POINTER(C.c_double), C.POINTER(C.c_size_t), C.POINTER(C.c_int)
 APPLY_P = C.CFUNCTYPE(None, PD, PD, C.c_size_t, PZ)
+# The device forms of the calls that stage R (include/iterative_solver_c.h): device addresses, this
+# rank's shard, row k at p + k * ld.
+DEVICE_SIG = {
+    "IterativeSolverHbmAddVectorDevice": (Z, [Z, P, P, Z]),
+    "IterativeSolverHbmSolutionDevice": (None, [I, PI, P, P, Z]),
+    "IterativeSolverHbmAddValueDevice": (Z, [D, P, P]),
+    "IterativeSolverHbmEndIterationDevice": (Z, [Z, P, P, Z]),
+    "IterativeSolverHbmSetDiagonalsDevice": (None, [P]),
+    "IterativeSolverHbmDiagonalsDevice": (None, [P]),
+}
+_ctx = None  # the context given to use_context
 
 
 def _load():
@@ -77,6 +89,10 @@ def _load():
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
             f.restype, f.argtypes = res, args
+        for name, (res, args) in DEVICE_SIG.items():  # declared only when the loaded library has them
+            f = getattr(lib, name, None)
+            if f is not None:
+                f.restype, f.argtypes = res, args
         lib.IterativeSolverHbmSetThrow(0)  # ctypes cannot unwind C++ exceptions: record them instead
         _lib = lib
     return _lib
@@ -84,6 +100,9 @@ def _load():
 
 def _call(name, *args):
     lib = _load()
+    # The flag is the process's, not this binding's: another user of the library in the same process (a
+    # Fortran or C++ caller) may have restored throwing, and an exception cannot unwind through ctypes.
+    lib.IterativeSolverHbmSetThrow(0)
     r = getattr(lib, name)(*args)
     err = lib.IterativeSolverHbmLastError()
     if err:
@@ -98,7 +117,38 @@ def _d(a):
 def use_context(ctx):
     """Run the instances created after this call on `ctx` (a subspace_hip.Context, possibly with a
     communicator attached); None restores the default single-rank context on device 0."""
+    global _ctx
     _call("IterativeSolverHbmSetContext", ctx.handle if ctx is not None else None)
+    _ctx = ctx
+
+
+def _dcall(name, *args):
+    if not hasattr(_load(), name):
+        raise RuntimeError(f"{name}: the loaded library has no device forms of the reverse-communication calls")
+    return _call(name, *args)
+
+
+def _is_device(a):
+    sh = sys.modules.get("subspace_hip")  # device arrays can only come from that module
+    return sh is not None and isinstance(a, (sh.DeviceRows, sh.DeviceVector))
+
+
+def _device_pair(solver, first, second):
+    """None for two numpy arrays; (rows, address, address, ld) for two device arrays of one shape
+    (subspace_hip.DeviceRows, or a DeviceVector where one row is meant).  A numpy array beside a device
+    array is a TypeError."""
+    if not _is_device(first) and not _is_device(second):
+        return None
+    if not (_is_device(first) and _is_device(second)):
+        raise TypeError("parameters and action/residual are both numpy arrays or both device arrays")
+    shapes = [(getattr(a, "m", 1), a.n, getattr(a, "ld", a.n)) for a in (first, second)]
+    if shapes[0] != shapes[1]:
+        raise ValueError(f"device arrays of different shapes (rows, length, ld): {shapes[0]} and {shapes[1]}")
+    if any(getattr(a, "dtype", np.float64) != np.float64 for a in (first, second)):
+        raise TypeError("device arrays are float64")
+    if shapes[0][1] != solver.local:
+        raise ValueError(f"device rows hold this rank's range of {solver.local} elements, not {shapes[0][1]}")
+    return shapes[0][0], first.ptr, second.ptr, shapes[0][2]
 
 
 def statistics():
@@ -122,6 +172,10 @@ class IterativeSolver:
         self.nroot = nroot
         self.value = None
         self._id = 0
+        self.offset, self.local = 0, n  # this rank's range, set by _register_range
+
+    def _register_range(self, rb, re):
+        self.offset, self.local = rb.value, re.value - rb.value
 
     def _register(self):
         """Called after the C layer pushed this object's instance: remember its id."""
@@ -160,22 +214,38 @@ class IterativeSolver:
     def solution(self, roots, parameters, residual, sync=True):
         self._check_top()
         roots_ = (C.c_int * max(1, len(roots)))(*roots)
+        dev = _device_pair(self, parameters, residual)
+        if dev is not None:
+            if dev[0] < len(roots):
+                raise ValueError("solution: fewer device rows than roots")
+            _dcall("IterativeSolverHbmSolutionDevice", len(roots), roots_, dev[1], dev[2], dev[3])
+            return self.value
         _call("IterativeSolverSolution", len(roots), roots_, _d(_flat(parameters)), _d(_flat(residual)), int(sync))
         return self.value
 
     def add_vector(self, parameters, action, sync=True):
         self._check_top()
+        dev = _device_pair(self, parameters, action)
+        if dev is not None:
+            return int(_dcall("IterativeSolverHbmAddVectorDevice", *dev))
         nbuffer = parameters.shape[0] if parameters.ndim > 1 else 1
         return int(_call("IterativeSolverAddVector", nbuffer, _d(_flat(parameters)), _d(_flat(action)), int(sync)))
 
     def add_value(self, value, parameters, action, sync=True):
         self._check_top()
-        r = int(_call("IterativeSolverAddValue", value, _d(_flat(parameters)), _d(_flat(action)), int(sync)))
+        dev = _device_pair(self, parameters, action)
+        if dev is not None:  # one row: the first of each array
+            r = int(_dcall("IterativeSolverHbmAddValueDevice", value, dev[1], dev[2]))
+        else:
+            r = int(_call("IterativeSolverAddValue", value, _d(_flat(parameters)), _d(_flat(action)), int(sync)))
         self.value = value
         return r
 
     def end_iteration(self, parameters, residual, sync=True):
         self._check_top()
+        dev = _device_pair(self, parameters, residual)
+        if dev is not None:
+            return int(_dcall("IterativeSolverHbmEndIterationDevice", *dev))
         nbuffer = parameters.shape[0] if parameters.ndim > 1 else 1
         return int(_call("IterativeSolverEndIteration", nbuffer, _d(_flat(parameters)), _d(_flat(residual)),
                          int(sync)))
@@ -235,6 +305,8 @@ class IterativeSolver:
         """One-call driver over the reverse-communication API, the loop of the reference's
         IterativeSolver.solve (iterative_solver_extension.pyx:78-165)."""
         self._check_top()
+        if _device_pair(self, parameters, actions) is not None:
+            return self._solve_device(parameters, actions, problem, generate_initial_guess, max_iter)
         if parameters.ndim < 2 or actions.ndim < 2:
             return self.solve(parameters.reshape([self.nroot, self.n]), actions.reshape([self.nroot, self.n]), problem,
                               generate_initial_guess, max_iter)
@@ -297,6 +369,79 @@ class IterativeSolver:
             if nwork < 1:
                 break
 
+    def _solve_device(self, parameters, actions, problem, generate_initial_guess, max_iter):
+        """solve() on device arrays (subspace_hip.DeviceRows of this rank's range): the same loop, with no
+        host copy of any vector.  problem.action / residual / diagonals receive device arrays (DeviceRows;
+        residual and diagonals one DeviceVector each), and Problem.precondition's default is
+        Context.precondition on the working rows with the working-set eigenvalues and the diagonals.
+        The default initial guess takes the nroot smallest diagonals with Context.select and writes unit
+        vectors with the sparse copy; select breaks a tie between equal diagonals towards the LARGER index,
+        where the host loop's argmin takes the first.  Rows must be 16-byte aligned (an even ld)."""
+        ctx = _ctx
+        if ctx is None or parameters.ctx is not ctx or actions.ctx is not ctx:
+            raise ValueError("solve() on device arrays: the arrays belong to the context given to use_context()")
+        if not hasattr(parameters, "m"):  # one DeviceVector each: one row
+            from subspace_hip import DeviceRows
+
+            parameters = DeviceRows(ctx, 1, parameters.n, ptr=parameters.ptr)
+            actions = DeviceRows(ctx, 1, actions.n, ptr=actions.ptr)
+        nbuffer = parameters.m
+        ev = np.zeros(self.nroot)
+        errors = np.zeros(self.nroot)
+        verbosity = _call("IterativeSolverVerbosity")
+        use_diagonals = problem.diagonals(actions.row(0))
+        if max_iter is not None:
+            _call("IterativeSolverSetMaxIter", int(max_iter))
+        if use_diagonals:
+            _dcall("IterativeSolverHbmSetDiagonalsDevice", actions.ptr)
+        if generate_initial_guess:
+            guess = []
+            if isinstance(self, LinearEigensystem):
+                if not use_diagonals:
+                    raise ValueError("Default initial guess requested, but diagonal elements are not available")
+                _dcall("IterativeSolverHbmDiagonalsDevice", actions.ptr)
+                idx, val = ctx.select(actions.row(0), self.nroot, offset=self.offset)
+                guess = [int(idx[k]) for k in np.argsort(val, kind="stable")]  # smallest diagonal first
+            elif isinstance(self, LinearEquations):
+                guess = list(range(self.nroot))
+            for i in range(nbuffer):  # zero, then the unit entry where this rank holds it
+                ctx.sparse_copy(parameters.row(i), guess[i:i + 1], [1.0] * len(guess[i:i + 1]), offset=self.offset)
+        nwork = nbuffer
+        value = None
+        for it in range(_call("IterativeSolverMaxIter")):
+            if _call("IterativeSolverNonLinear") > 0:
+                value = problem.residual(parameters.row(0), actions.row(0))
+                if isinstance(self, Optimize):
+                    nwork = self.add_value(value, parameters, actions)
+                else:
+                    nwork = self.add_vector(parameters.row(0), actions.row(0))
+            else:
+                problem.action(parameters, actions)
+                nwork = self.add_vector(parameters.head(nwork), actions.head(nwork))
+            while self.end_iteration_needed:
+                if nwork > 0:
+                    _call("IterativeSolverWorkingSetEigenvalues", _d(ev))
+                    if use_diagonals:
+                        # as the host loop: the diagonals pass through the first parameter row
+                        _dcall("IterativeSolverHbmDiagonalsDevice", parameters.ptr)
+                        problem.precondition(actions.head(nwork), shift=ev[:nwork], diagonals=parameters.row(0))
+                    else:
+                        problem.precondition(actions.head(nwork), shift=ev[:nwork])
+                nwork = self.end_iteration(parameters, actions)
+            _call("IterativeSolverErrors", _d(errors))
+            self.value = _call("IterativeSolverValue")
+            if _call("IterativeSolverHasValues") != 0:
+                reported = problem.report(it + 1 if nwork > 0 else 0, verbosity, errors, value=value)
+            elif _call("IterativeSolverHasEigenvalues") != 0:
+                _call("IterativeSolverEigenvalues", _d(ev))
+                reported = problem.report(it + 1 if nwork > 0 else 0, verbosity, errors, eigenvalues=ev[:self.nroot])
+            else:
+                reported = problem.report(it + 1 if nwork > 0 else 0, verbosity, errors)
+            if not reported and verbosity >= 2:
+                print("Iteration", it, "log10(|residual|)=", np.log10(errors))
+            if nwork < 1:
+                break
+
 
 _m_mpicomm_compute = None
 
@@ -327,6 +472,7 @@ class LinearEigensystem(IterativeSolver):
               1 if hermitian else 0, verbosity, pname.encode(), _comm(mpicomm), algorithm.encode(),
               options.encode())
         self._register()
+        self._register_range(rb, re)
         if range is not None:
             range[0], range[1] = rb.value, re.value
 
@@ -345,6 +491,7 @@ class NonLinearEquations(IterativeSolver):
         _call("IterativeSolverNonLinearEquationsInitialize", n, C.byref(rb), C.byref(re), thresh, verbosity,
               pname.encode(), _comm(mpicomm), algorithm.encode(), options.encode())
         self._register()
+        self._register_range(rb, re)
         if range is not None:
             range[0], range[1] = rb.value, re.value
 
@@ -361,6 +508,7 @@ class LinearEquations(IterativeSolver):
               thresh_value, 1 if hermitian else 0, verbosity, pname.encode(), _comm(mpicomm), algorithm.encode(),
               options.encode())
         self._register()
+        self._register_range(rb, re)
 
 
 class Optimize(IterativeSolver):
@@ -371,3 +519,4 @@ class Optimize(IterativeSolver):
         _call("IterativeSolverOptimizeInitialize", n, C.byref(rb), C.byref(re), thresh, thresh_value, verbosity,
               1 if minimize else 0, pname.encode(), _comm(mpicomm), algorithm.encode(), options.encode())
         self._register()
+        self._register_range(rb, re)

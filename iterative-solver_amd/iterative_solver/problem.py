@@ -27,6 +27,14 @@ class Problem:
     def precondition(self, residual, shift=None, diagonals=None):
         """Turn residual rows into update steps in place.  Default: divide by the diagonals plus
         the shift plus 1e-14, row by row (reference problem.py:55-82 uses exactly this form)."""
+        if hasattr(residual, "ptr"):
+            # device rows (solve() on subspace_hip.DeviceRows): Context.precondition on the rows, in HBM --
+            # residual_k / ((diagonals - shift_k) + 1e-15), the C++ solvers' preconditioner
+            if diagonals is None:
+                raise NotImplementedError
+            rows = residual.rows() if hasattr(residual, "rows") else [residual]
+            residual.ctx.precondition(rows, diagonals, np.zeros(len(rows)) if shift is None else shift)
+            return
         small = 1e-14
         if residual.ndim > 1:
             for i in range(residual.shape[0]):

@@ -56,6 +56,8 @@ EXPORTS = [
     "ssp_q32_gemm_inner_cols", "ssp_q32_construct_solution", "ssp_q32_block_update",
     # the refined f32 Q space: f64 vectors rounded through f32 in place
     "ssp_quantise_f32",
+    # a caller's row-major block of vectors into and out of library vectors, device to device
+    "ssp_rows_import", "ssp_rows_export",
 ]
 
 # The mixed-precision entry points are optional in a loaded library: the CPU emulation of the f64 C ABI
@@ -67,6 +69,9 @@ OPTIONAL = frozenset(n for n in EXPORTS if n.endswith("_f32") or n.startswith("s
 # The fused passes over an f32 Q space are tolerated in the same way (absent from the emulation, a call
 # raises SspError(SSP_ERR_UNSUPPORTED)); they are a set of their own: OPTIONAL stays the storage layer.
 OPTIONAL_Q32 = frozenset(n for n in EXPORTS if n.startswith("ssp_q32_"))
+# The row-block entry points (a caller's device block <-> library vectors), optional in the same way and a
+# set of their own: the three sets above stay what they were.
+OPTIONAL_ROWS = frozenset({"ssp_rows_import", "ssp_rows_export"})
 SSP_F64, SSP_F32 = 0, 1
 
 
@@ -196,9 +201,12 @@ def _declare(lib):
         "ssp_q32_gemm_inner_cols": (I, [P, P, PD, I, P, C.POINTER(I), PD, I, Z, PD]),
         "ssp_q32_construct_solution": (I, [P, PD, PZ, PZ, PD, I, PD, P, I, P, I, Z, Z]),
         "ssp_q32_block_update": (I, [P, PD, PZ, PZ, PD, I, PD, P, I, P, PD, I, Z, Z]),
+        "ssp_rows_import": (I, [P, P, Z, P, I, Z]),
+        "ssp_rows_export": (I, [P, P, PD, I, P, Z, Z]),
     }
+    optional = OPTIONAL | OPTIONAL_Q32 | OPTIONAL_REFINED | OPTIONAL_ROWS
     for name, (res, args) in sig.items():
-        if (name in OPTIONAL or name in OPTIONAL_Q32 or name in OPTIONAL_REFINED) and not hasattr(lib, name):
+        if name in optional and not hasattr(lib, name):
             continue
         f = getattr(lib, name)
         f.restype = res
@@ -434,6 +442,61 @@ class DeviceVector:
 
     def __len__(self):
         return self.n
+
+
+class DeviceRows:
+    """m rows of n doubles, row k at element k * ld of ONE device allocation: the row-major block the
+    device forms of the reverse-communication API take (iterative_solver, include/iterative_solver_c.h).
+    The default ld is n rounded up to even, so every row is 16-byte aligned and row(k) can go to any
+    Context op.  With ptr (a device address, 8-byte aligned) the object is a view of memory it does not
+    own: any ld >= n, rows possibly at 8 mod 16, which only rows_import / rows_export accept."""
+
+    def __init__(self, ctx: "Context", m: int, n: int, ld: int = None, *, ptr: int = None):
+        ld = n + (n & 1) if ld is None else int(ld)
+        if m < 0 or n < 0 or ld < n:
+            raise ValueError("DeviceRows: m >= 0, n >= 0 and ld >= n")
+        self.ctx, self.m, self.n, self.ld = ctx, m, n, ld
+        self._block = None
+        if ptr is None:
+            self._block = ctx.alloc(max_(m * ld))
+            ptr = self._block.ptr
+        self.ptr = ptr
+
+    def row(self, k: int) -> DeviceVector:
+        """Row k as a DeviceVector that does not own its memory."""
+        if not 0 <= k < self.m:
+            raise IndexError(k)
+        return DeviceVector(self.ctx, self.n, self.ptr + 8 * k * self.ld, owner=False)
+
+    def rows(self):
+        return [self.row(k) for k in range(self.m)]
+
+    def head(self, m: int) -> "DeviceRows":
+        """The first m rows, as a view."""
+        if not 0 <= m <= self.m:
+            raise IndexError(m)
+        return DeviceRows(self.ctx, m, self.n, self.ld, ptr=self.ptr)
+
+    def upload(self, a: np.ndarray):
+        """Rows from a host array of m x n (or n, for one row); the padding [n, ld) is not touched."""
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(self.m, self.n)
+        for k in range(self.m):
+            _check(self.ctx.lib.ssp_upload(self.ctx.handle, self.ptr + 8 * k * self.ld, a[k].ctypes.data, self.n))
+
+    def numpy(self) -> np.ndarray:
+        out = np.empty((self.m, self.n))
+        for k in range(self.m):
+            _check(self.ctx.lib.ssp_download(self.ctx.handle, out[k].ctypes.data, self.ptr + 8 * k * self.ld, self.n))
+        return out
+
+    def free(self):
+        if self._block is not None:
+            self._block.free()
+            self._block = None
+        self.ptr = 0
+
+    def __len__(self):
+        return self.m
 
 
 class Context:
@@ -834,6 +897,28 @@ class Context:
         n = yy[0].n if yy else 0
         _check(f(self.handle, _dptr(alphas), _ptrs(xx), _same_dtype(xx), _dptr(a), len(xx), _ptrs(yy),
                  _same_dtype(yy), len(yy), n, int(bool(set))))
+
+    # -- row blocks (include/subspace_hip.h ssp_rows_*): a caller's device block <-> library vectors ---
+    def _rows(self, name: str):
+        f = getattr(self.lib, name, None)
+        if f is None:
+            raise SspError(7, f"{name}: the loaded library has no row-block entry points")
+        return f
+
+    def rows_import(self, rows: DeviceRows, dst: Sequence[DeviceVector]):
+        """dst[k] = row k of rows, k < len(dst) (ssp_rows_import: a bit copy, one pass)."""
+        f = self._rows("ssp_rows_import")
+        if len(dst) > rows.m or any(v.n != rows.n for v in dst):
+            raise ValueError("rows_import: one vector of the rows' length per row")
+        _check(f(self.handle, rows.ptr, rows.ld, _ptrs(dst), len(dst), rows.n))
+
+    def rows_export(self, src: Sequence[DeviceVector], rows: DeviceRows, xs=None):
+        """row k of rows = xs[k] * src[k], k < len(src) (ssp_rows_export; xs None: bit copies)."""
+        f = self._rows("ssp_rows_export")
+        if len(src) > rows.m or any(v.n != rows.n for v in src):
+            raise ValueError("rows_export: one vector of the rows' length per row")
+        a = None if xs is None else self._scales(xs, len(src))
+        _check(f(self.handle, _ptrs(src), None if a is None else _dptr(a), len(src), rows.ptr, rows.ld, rows.n))
 
     # -- fused solver passes over an f32 Q space (include/subspace_hip.h ssp_q32_*) -----------------
     def q32_gemm_inner_cols(self, rows, cols, xs=None, ys=None) -> np.ndarray:
