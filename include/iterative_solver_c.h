@@ -167,6 +167,67 @@ size_t IterativeSolverHbmEndIterationDevice(size_t buffer_size, double* solution
 void IterativeSolverHbmSetDiagonalsDevice(const double* diagonals);
 void IterativeSolverHbmDiagonalsDevice(double* diagonals);
 
+/* ---- extension: the Q space in f32, and refined residuals -----------------------------------
+ * Two options of IterativeSolverLinearEigensystemInitialize's `options` string, for the one-rank "Davidson"
+ * (an instance that names neither is what it always was):
+ *   Q_STORAGE=f32   (default f64) the Q vectors are stored in 4 bytes per element: half the HBM and half the
+ *                   bytes of every pass over them; all arithmetic stays FP64 (include/itsolv_hbm.h *_q32).
+ *                   Thresholds are meaningful down to about 1e-6 |H|; below that the solve stalls.
+ *   Q_REFINE=1      with optional Q_REFINE_KAPPA=<kappa> (default 8): the refined mode of
+ *                   itsolv_hbm/solvers.h set_refine.  A root whose residual estimate the rounding of the stored
+ *                   actions no longer vouches for gets its residual from the action of its own solution, which
+ *                   the caller supplies through IterativeSolverHbmSetRefineAction; with it an f32 Q space
+ *                   reaches f64 thresholds (1e-10).  Allowed with Q_STORAGE=f64 too: nothing is rounded there
+ *                   (delta = 0), and the only effect is that a root is declared converged on the residual of
+ *                   its solution's own action.
+ * Refused, each with an error that names the option (recorded, not thrown, after IterativeSolverHbmSetThrow(0)):
+ * an unknown Q_STORAGE value; either option on LinearEquations, NonLinearEquations, Optimize or RSPT; either
+ * option on an instance with more than one rank; Q_REFINE with hermitian = 0, MAX_SIZE_QSPACE, RESET_D or
+ * RESET_D_MAX_Q_SIZE (the refined mode has no D space); Q_STORAGE=f32 over a vector library without the
+ * mixed-precision ABI.  Out of scope: multi-rank f32 instances, a D space or a Q-space limit in refined mode,
+ * f32 Q for the other solver families, a Fortran binding of the refine callback (the Fortran module passes
+ * `options` through, so the plain Q_STORAGE=f32 works from Fortran), a device-side apply_on_p.
+ *
+ * The refine action.  fn(nvec, parameters, action, ld, user) must set action row k = H * parameters row k for
+ * k < nvec (row k at p + k*ld).  It is called from inside IterativeSolverAddVector, its device form and
+ * IterativeSolverAddP, at most once per batch of roots, with nvec <= the call's buffer_size, and its two arrays
+ * ARE that call's own `parameters` and `action`: the layer writes the nvec selected solutions, compacted, into
+ * rows [0, nvec) of `parameters`, calls fn, and reads rows [0, nvec) of `action`.  For a host call ld =
+ * dimension and the arrays are host memory; for a device call ld is the call's ld, both are device memory and
+ * the stream contract is that of the device forms (fn's work ordered on the context stream, or finished, when
+ * it returns).  The call then completes and writes every row of both arrays as it always does, so the caller's
+ * arrays end as they would without a refinement; no other memory is used.  A refinement that is needed while no
+ * action is set is an error naming this call.
+ *
+ * Rounding before the action.  The scheme rests on a_j = H q_j holding for the vector q_j the Q space STORES,
+ * so with Q_STORAGE=f32 and Q_REFINE the first `result` parameter rows IterativeSolverEndIteration (and its
+ * device form) returns are rounded to binary32-representable values, (double)(float)(s*x) -- on the device
+ * route by the export itself (ssp_rows_export_quantised), at no extra pass.  The remaining rows and every
+ * residual row are as without the option.  The initial guess is the caller's: unit vectors need nothing; any
+ * other guess goes through IterativeSolverHbmQuantise[Device] before its action is formed.  A guess that is not
+ * representable leaves the stored pair (q, a) inconsistent at 2^-24 |H|: the solve then stalls above the
+ * threshold; it does not report a false residual, because refined errors are true ones.
+ *
+ * Diagonals.  With actions stored rounded, the residual of a unit-vector guess is rounding noise at the guess's
+ * index (2^-24 |a|, where f64 arithmetic gives an exact zero), and the usual preconditioner r / ((d - theta) +
+ * 1e-15) must not meet it with an exact zero denominator.  The C++ solve() keeps the problem's diagonals in a Q
+ * vector; an instance with Q_STORAGE=f32 does the same: IterativeSolverSetDiagonals[Device] rounds them to the Q
+ * storage, and IterativeSolverDiagonals[Device] returns them so.  A caller that holds its own diagonals
+ * preconditions with their rounded values, or regularises its denominator. */
+typedef void (*itsolv_refine_action_fn)(size_t nvec, const double* parameters, double* action, size_t ld, void* user);
+/* The refine action of the top instance; NULL clears it.  Returns 0, or 1 (IterativeSolverHbmLastError). */
+int IterativeSolverHbmSetRefineAction(itsolv_refine_action_fn fn, void* user);
+/* Of the top instance: actions spent on refined residuals, the iteration (from 1) of the first (0: none), the
+ * largest delta (the bound on |estimate - true residual|) of the last iteration.  Returns 0; 1: no instance. */
+int IterativeSolverHbmRefineStatistics(int* refined_actions, int* first_refined_iteration, double* max_delta);
+/* Bytes per stored Q element of the top instance: 8 or 4; 0 when there is none. */
+size_t IterativeSolverHbmQStorage(void);
+/* Rounds `buffer_size` parameter rows in place to the Q storage format of the top instance (host rows of
+ * length `dimension`; device rows of this rank's shard, row k at p + k*ld).  Returns the number of rows
+ * rounded: 0 with Q_STORAGE=f64, where there is nothing to round. */
+size_t IterativeSolverHbmQuantise(size_t buffer_size, double* parameters);
+size_t IterativeSolverHbmQuantiseDevice(size_t buffer_size, double* parameters, size_t ld);
+
 #ifdef __cplusplus
 }
 #endif

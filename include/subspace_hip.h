@@ -294,6 +294,15 @@ int ssp_block_update(ssp_ctx* ctx, const double* palphas, const size_t* ptr, con
 int ssp_rows_import(ssp_ctx* ctx, const double* src, size_t ld, double* const* dst, int m, size_t n);
 /* dst[k*ld + i] = xs[k] * src[k][i],  xs NULL = all 1 */
 int ssp_rows_export(ssp_ctx* ctx, const double* const* src, const double* xs, int m, double* dst, size_t ld, size_t n);
+/* The export that rounds: dst[k*ld + i] = (double)(float)(xs[k] * src[k][i]) for k < mq, and
+ * xs[k] * src[k][i] as ssp_rows_export for mq <= k < m.  The rounding is ssp_quantise_f32's (to nearest
+ * even, binary32 subnormals kept, overflow to +-inf), so the bits are those of ssp_quantise_f32 on copies
+ * of the first mq vectors followed by ssp_rows_export -- in one pass of 16 bytes per element and row
+ * instead of 32, and the sources are not written.  The refined f32 Q space of the reverse-communication
+ * API returns its new parameter rows through it (include/iterative_solver_c.h).  Same shapes, launches
+ * and argument checks as ssp_rows_export; mq < 0 or mq > m is SSP_ERR_ARG.  Ledger name rows_export_q. */
+int ssp_rows_export_quantised(ssp_ctx* ctx, const double* const* src, const double* xs, int m, int mq, double* dst,
+                              size_t ld, size_t n);
 
 /* ---- mixed precision: vectors STORED in binary32, all arithmetic in FP64 (csrc/kernels_mixed.hip).
  *      The Q space of a solve is written once and afterwards only read; held in f32 it takes half

@@ -11,6 +11,8 @@
 //                   side's element pairs); the same two shapes, windows of the same bytes per wave.
 // One launch moves up to kRowsMax rows (blockIdx.y is the row); pointers and scales ride in the kernel
 // argument block.  A row is a bit copy, or with a scale s != 1 the single product x * s of k_copy<true>.
+// ssp_rows_export_quantised is the export with the first mq rows rounded through binary32 as they are stored,
+// (double)(float)(x * s): k_quantise_f32's value in the export's pass, the same four shapes (k_rows_q).
 #include <algorithm>
 #include <string>
 
@@ -35,17 +37,19 @@ __device__ __forceinline__ double2 ld2(const double* p) { return *reinterpret_ca
 __device__ __forceinline__ void st2(double* p, double2 v) { *reinterpret_cast<double2*>(p) = v; }
 __device__ __forceinline__ double ld1nt(const double* p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ void st1nt(double* p, double v) { __builtin_nontemporal_store(v, p); }
-template <bool SC>
-__device__ __forceinline__ double2 sc2(double2 v, double s) {
-  return SC ? make_double2(v.x * s, v.y * s) : v;
-}
-template <bool SC>
+// QT: the product (or the element) rounded through binary32, the value k_quantise_f32 stores.
+template <bool SC, bool QT = false>
 __device__ __forceinline__ double sc1(double v, double s) {
-  return SC ? v * s : v;
+  const double p = SC ? v * s : v;
+  return QT ? double(float(p)) : p;
+}
+template <bool SC, bool QT = false>
+__device__ __forceinline__ double2 sc2(double2 v, double s) {
+  return make_double2(sc1<SC, QT>(v.x, s), sc1<SC, QT>(v.y, s));
 }
 
 // Both sides 16-byte aligned: k_copy's loop (WIN: k_copy_win's).
-template <bool SC, bool WIN>
+template <bool SC, bool WIN, bool QT = false>
 __device__ __forceinline__ void row_copy16(double* __restrict__ x, const double* __restrict__ y, size_t n, double s) {
   using ssp::ld2nt;
   using ssp::st2nt;
@@ -57,9 +61,9 @@ __device__ __forceinline__ void row_copy16(double* __restrict__ x, const double*
 #pragma unroll
           for (int u = 0; u < kWinU; ++u) v[u] = ld2nt(y + 2 * (p0 + 64 * u));
 #pragma unroll
-          for (int u = 0; u < kWinU; ++u) st2nt(x + 2 * (p0 + 64 * u), sc2<SC>(v[u], s));
+          for (int u = 0; u < kWinU; ++u) st2nt(x + 2 * (p0 + 64 * u), sc2<SC, QT>(v[u], s));
         },
-        [&](size_t i) { st2(x + 2 * i, sc2<SC>(ld2(y + 2 * i), s)); }, [&](size_t e) { x[e] = sc1<SC>(y[e], s); });
+        [&](size_t i) { st2(x + 2 * i, sc2<SC, QT>(ld2(y + 2 * i), s)); }, [&](size_t e) { x[e] = sc1<SC, QT>(y[e], s); });
     return;
   }
   const size_t n2 = n >> 1;
@@ -68,19 +72,19 @@ __device__ __forceinline__ void row_copy16(double* __restrict__ x, const double*
   for (; i + 3 * stride < n2; i += 4 * stride) {
     double2 a0 = ld2nt(y + 2 * i), a1 = ld2nt(y + 2 * (i + stride)), a2 = ld2nt(y + 2 * (i + 2 * stride)),
             a3 = ld2nt(y + 2 * (i + 3 * stride));
-    st2nt(x + 2 * i, sc2<SC>(a0, s));
-    st2nt(x + 2 * (i + stride), sc2<SC>(a1, s));
-    st2nt(x + 2 * (i + 2 * stride), sc2<SC>(a2, s));
-    st2nt(x + 2 * (i + 3 * stride), sc2<SC>(a3, s));
+    st2nt(x + 2 * i, sc2<SC, QT>(a0, s));
+    st2nt(x + 2 * (i + stride), sc2<SC, QT>(a1, s));
+    st2nt(x + 2 * (i + 2 * stride), sc2<SC, QT>(a2, s));
+    st2nt(x + 2 * (i + 3 * stride), sc2<SC, QT>(a3, s));
   }
-  for (; i < n2; i += stride) st2(x + 2 * i, sc2<SC>(ld2(y + 2 * i), s));
-  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = sc1<SC>(y[n - 1], s);
+  for (; i < n2; i += stride) st2(x + 2 * i, sc2<SC, QT>(ld2(y + 2 * i), s));
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = sc1<SC, QT>(y[n - 1], s);
 }
 
 // One side at 8 mod 16: the same two shapes over single elements.  WIN: a wave owns 2 kWinU x 64
 // consecutive elements per visit (the kWinU KiB of row_copy16's window), whole windows first, then the
 // elements past the last whole window, thread-granular.
-template <bool SC, bool WIN>
+template <bool SC, bool WIN, bool QT = false>
 __device__ __forceinline__ void row_copy8(double* __restrict__ x, const double* __restrict__ y, size_t n, double s) {
   if (WIN) {
     constexpr int U = 2 * kWinU;
@@ -94,10 +98,10 @@ __device__ __forceinline__ void row_copy8(double* __restrict__ x, const double* 
 #pragma unroll
       for (int u = 0; u < U; ++u) v[u] = ld1nt(y + e0 + 64 * u);
 #pragma unroll
-      for (int u = 0; u < U; ++u) st1nt(x + e0 + 64 * u, sc1<SC>(v[u], s));
+      for (int u = 0; u < U; ++u) st1nt(x + e0 + 64 * u, sc1<SC, QT>(v[u], s));
     }
     for (size_t e = nwin * win + size_t(blockIdx.x) * kBlock + threadIdx.x; e < n; e += size_t(gridDim.x) * kBlock)
-      x[e] = sc1<SC>(y[e], s);
+      x[e] = sc1<SC, QT>(y[e], s);
     return;
   }
   const size_t stride = size_t(gridDim.x) * kBlock;
@@ -105,12 +109,12 @@ __device__ __forceinline__ void row_copy8(double* __restrict__ x, const double* 
   for (; i + 3 * stride < n; i += 4 * stride) {
     const double a0 = ld1nt(y + i), a1 = ld1nt(y + i + stride), a2 = ld1nt(y + i + 2 * stride),
                  a3 = ld1nt(y + i + 3 * stride);
-    st1nt(x + i, sc1<SC>(a0, s));
-    st1nt(x + i + stride, sc1<SC>(a1, s));
-    st1nt(x + i + 2 * stride, sc1<SC>(a2, s));
-    st1nt(x + i + 3 * stride, sc1<SC>(a3, s));
+    st1nt(x + i, sc1<SC, QT>(a0, s));
+    st1nt(x + i + stride, sc1<SC, QT>(a1, s));
+    st1nt(x + i + 2 * stride, sc1<SC, QT>(a2, s));
+    st1nt(x + i + 3 * stride, sc1<SC, QT>(a3, s));
   }
-  for (; i < n; i += stride) x[i] = sc1<SC>(y[i], s);
+  for (; i < n; i += stride) x[i] = sc1<SC, QT>(y[i], s);
 }
 
 // dst[r] = s[r] * src[r], row r = blockIdx.y; parity and scale are uniform over the row's workgroups.
@@ -130,9 +134,36 @@ __global__ __launch_bounds__(kBlock) void k_rows(const RowsArgs a) {
   }
 }
 
+// k_rows with rows [0, mq) of the launch rounded through binary32 as they are stored (the export that
+// rounds, ssp_rows_export_quantised): the same four shapes, the rounding in place of nothing.
+struct RowsQArgs {
+  RowsArgs r;
+  int mq;
+};
+
+template <bool WIN, bool QT>
+__device__ __forceinline__ void row_any(double* x, const double* y, size_t n, double s) {
+  const bool mis = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) != 0;
+  if (!mis) {
+    if (s == 1.0) row_copy16<false, WIN, QT>(x, y, n, s);
+    else row_copy16<true, WIN, QT>(x, y, n, s);
+  } else {
+    if (s == 1.0) row_copy8<false, WIN, QT>(x, y, n, s);
+    else row_copy8<true, WIN, QT>(x, y, n, s);
+  }
+}
+
+template <bool WIN>
+__global__ __launch_bounds__(kBlock) void k_rows_q(const RowsQArgs a) {
+  const int r = blockIdx.y;
+  if (r < a.mq) row_any<WIN, true>(a.r.dst[r], a.r.src[r], a.r.n, a.r.s[r]);
+  else row_any<WIN, false>(a.r.dst[r], a.r.src[r], a.r.n, a.r.s[r]);
+}
+
 // Rows [r0, r0 + mm) of one call, already checked: one launch.  The grid of one row is k_copy's for n
 // elements; the rows together stay within that rule's workgroups per CU (grid-stride beyond).
-int launch_rows(ssp_ctx* ctx, const char* op, const RowsArgs& a, int mm) {
+// mq >= 0: the first mq rows of the launch are rounded (k_rows_q).
+int launch_rows(ssp_ctx* ctx, const char* op, const RowsArgs& a, int mm, int mq = -1) {
   const size_t n = a.n;
   const bool win = n >= kWinMin;
   const unsigned per_cu = win ? 16 : 64;
@@ -141,6 +172,13 @@ int launch_rows(ssp_ctx* ctx, const char* op, const RowsArgs& a, int mm) {
   if (size_t(gx) * size_t(mm) > cap) gx = std::max(1u, cap / unsigned(mm));
   ssp::LedgerScope ls(ctx, op, 16.0 * mm * n);
   const dim3 g(gx, unsigned(mm));
+  if (mq >= 0) {
+    const RowsQArgs q{a, mq};
+    if (win) SSP_LAUNCH(k_rows_q<true>, g, dim3(kBlock), 0, ctx->stream, q);
+    else SSP_LAUNCH(k_rows_q<false>, g, dim3(kBlock), 0, ctx->stream, q);
+    SSP_TRY_HIP(hipGetLastError());
+    return SSP_OK;
+  }
   if (win) SSP_LAUNCH(k_rows<true>, g, dim3(kBlock), 0, ctx->stream, a);
   else SSP_LAUNCH(k_rows<false>, g, dim3(kBlock), 0, ctx->stream, a);
   SSP_TRY_HIP(hipGetLastError());
@@ -211,6 +249,30 @@ int ssp_rows_export(ssp_ctx* ctx, const double* const* src, const double* xs, in
     }
     a.n = n;
     SSP_TRY(launch_rows(ctx, "rows_export", a, mm));
+  }
+  return SSP_OK;
+}
+
+int ssp_rows_export_quantised(ssp_ctx* ctx, const double* const* src, const double* xs, int m, int mq, double* dst,
+                              size_t ld, size_t n) {
+  SSP_CHECK_CTX_KEEP_FILLS(ctx);
+  SSP_TRY(check_rows("ssp_rows_export_quantised", dst, ld, src, m, n));
+  if (mq < 0 || mq > std::max(m, 0)) return bad("ssp_rows_export_quantised", "mq outside [0, m]");
+  if (m <= 0 || n == 0) return SSP_OK;
+  for (int k = 0; k < m; ++k) {
+    SSP_TRY(ssp::flush_fills_over(ctx, src[k], n));
+    SSP_TRY(ssp::overwrite_fills(ctx, dst + size_t(k) * ld, n));
+  }
+  for (int r0 = 0; r0 < m; r0 += kRowsMax) {
+    RowsArgs a{};
+    const int mm = std::min(kRowsMax, m - r0);
+    for (int r = 0; r < mm; ++r) {
+      a.src[r] = src[r0 + r];
+      a.dst[r] = dst + size_t(r0 + r) * ld;
+      a.s[r] = xs ? xs[r0 + r] : 1.0;
+    }
+    a.n = n;
+    SSP_TRY(launch_rows(ctx, "rows_export_q", a, mm, std::min(mm, std::max(0, mq - r0))));
   }
   return SSP_OK;
 }

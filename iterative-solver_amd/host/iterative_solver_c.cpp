@@ -20,6 +20,7 @@
 #include "itsolv_hbm/solver_factory.h"
 #include "itsolv_hbm/solvers.h"
 #include "mpi_bridge.h"
+#include "rc_solver.h"
 
 using molpro::linalg::hbm::check;
 using molpro::linalg::hbm::Device;
@@ -31,12 +32,16 @@ namespace it = molpro::linalg::itsolv;
 extern "C" {
 int ssp_rows_import(ssp_ctx*, const double*, size_t, double* const*, int, size_t) __attribute__((weak));
 int ssp_rows_export(ssp_ctx*, const double* const*, const double*, int, double*, size_t, size_t) __attribute__((weak));
+int ssp_rows_export_quantised(ssp_ctx*, const double* const*, const double*, int, int, double*, size_t, size_t)
+    __attribute__((weak));
 }
 
 namespace {
 
 const auto rows_import_fn = &ssp_rows_import;
 const auto rows_export_fn = &ssp_rows_export;
+const auto rows_export_q_fn = &ssp_rows_export_quantised;
+const auto make_q32_fn = &itsolv_rc::make_rc_davidson_q32;  // null without host_q32/ (rc_solver.h)
 
 using Solver = it::IterativeSolverTemplate<Vec, Vec, SparseP>;
 using Davidson = it::LinearEigensystemDavidson<Vec, Vec, SparseP>;
@@ -54,13 +59,20 @@ bool g_throw = true;
 struct Instance {
   uint64_t id = 0;  // IterativeSolverHbmInstanceId: lets a binding finalize its own instance
   std::shared_ptr<Device> dev;
-  std::unique_ptr<Solver> solver;
+  std::unique_ptr<itsolv_rc::RcSolver> solver;  // the Q-independent face: Q is Vec, or VecF32 (Q_STORAGE=f32)
   size_t dimension = 0, offset = 0, local = 0;
   std::vector<Vec> rp, ra;  // HBM staging of the caller's R vectors (grown on demand)
   Apply_on_p_fort apply_on_p_fort = nullptr;
   std::unique_ptr<Vec> diagonals;
   bool has_values = false;
   bool has_eigenvalues = false;
+  // refined mode (Q_REFINE): the caller's action, and the arrays of the running AddVector / AddP call that
+  // serve as its scratch (RefineScratch below)
+  itsolv_refine_action_fn refine_fn = nullptr;
+  void* refine_user = nullptr;
+  double *scratch_p = nullptr, *scratch_a = nullptr;
+  size_t scratch_ld = 0;
+  bool scratch_device = false;
 };
 // The instance stack (reference IterativeSolverCMPI.cpp: std::stack<Instance>); the back is the top,
 // the only active instance.  A vector, so that IterativeSolverHbmFinalizeInstance can also remove
@@ -177,13 +189,21 @@ void import_rows(Instance& in, std::vector<Vec>& v, size_t nvec, const double* d
   }
   for (size_t k = 0; k < nvec; ++k) check(ssp_copy(in.dev->ctx(), dst[k], dev + k * ld, in.local), "ssp_copy");
 }
-void export_rows(Instance& in, const std::vector<Vec>& v, size_t nvec, double* dev, size_t ld) {
+// mq > 0: the first mq rows are rounded to the Q storage format as they are stored (the caller has checked
+// that the loaded library has the export that rounds).
+void export_list(Instance& in, const std::vector<const Vec*>& v, double* dev, size_t ld, size_t mq = 0) {
+  const size_t nvec = v.size();
   if (nvec == 0 || in.local == 0) return;
   std::vector<const double*> src(nvec);
   std::vector<double> xs(nvec);
   for (size_t k = 0; k < nvec; ++k) {
-    src[k] = v[k].data_deferred();
-    xs[k] = v[k].scale();
+    src[k] = v[k]->data_deferred();
+    xs[k] = v[k]->scale();
+  }
+  if (mq > 0) {
+    check(rows_export_q_fn(in.dev->ctx(), src.data(), xs.data(), int(nvec), int(mq), dev, ld, in.local),
+          "ssp_rows_export_quantised");
+    return;
   }
   if (rows_export_fn) {
     check(rows_export_fn(in.dev->ctx(), src.data(), xs.data(), int(nvec), dev, ld, in.local), "ssp_rows_export");
@@ -193,6 +213,11 @@ void export_rows(Instance& in, const std::vector<Vec>& v, size_t nvec, double* d
     if (xs[k] == 1.0) check(ssp_copy(in.dev->ctx(), dev + k * ld, src[k], in.local), "ssp_copy");
     else check(ssp_scal_copy(in.dev->ctx(), xs[k], dev + k * ld, src[k], in.local), "ssp_scal_copy");
   }
+}
+void export_rows(Instance& in, const std::vector<Vec>& v, size_t nvec, double* dev, size_t ld, size_t mq = 0) {
+  std::vector<const Vec*> list(nvec);
+  for (size_t k = 0; k < nvec; ++k) list[k] = &v[k];
+  export_list(in, list, dev, ld, mq);
 }
 // Both arrays of a device call, checked before either is staged.
 void check_pair(const Instance& in, size_t nvec, const double* a, const double* b, size_t ld, const char* what) {
@@ -221,6 +246,102 @@ void synchronize(Instance& in, size_t nvec, double* host) {
 }
 
 it::VecRef<Vec> first(std::vector<Vec>& v, size_t n) { return it::wrap(v.begin(), v.begin() + long(n)); }
+
+// ---- refined mode (Q_REFINE; include/iterative_solver_c.h) ------------------------------------------------
+// The arrays of the running AddVector / AddVectorDevice / AddP call are the scratch of a refinement inside it:
+// the call exports every row at its end, so what the refinement leaves in them is overwritten.
+struct RefineScratch {
+  Instance& in;
+  RefineScratch(Instance& i, double* p, double* a, size_t ld, bool device) : in(i) {
+    in.scratch_p = p;
+    in.scratch_a = a;
+    in.scratch_ld = ld;
+    in.scratch_device = device;
+  }
+  ~RefineScratch() { in.scratch_p = in.scratch_a = nullptr; }
+};
+
+// The solver's refine action (IterativeSolverTemplate::set_refine_action): the m selected solutions, compacted,
+// into rows [0, m) of the call's parameters (pending scales applied), the caller's action on them, rows [0, m)
+// of its action array into the solver's vectors.
+void refine_action(Instance& in, const it::CVecRef<Vec>& x, const it::VecRef<Vec>& a) {
+  const size_t m = x.size();
+  if (!in.refine_fn || !in.scratch_p || !in.scratch_a)
+    throw std::logic_error("refine: no IterativeSolverHbmSetRefineAction callback for this call");
+  double* const p = in.scratch_p;
+  double* const g = in.scratch_a;
+  const size_t ld = in.scratch_ld;
+  if (in.scratch_device) {
+    std::vector<const Vec*> src(m);
+    for (size_t k = 0; k < m; ++k) src[k] = &x[k].get();
+    export_list(in, src, p, ld);
+    in.refine_fn(m, p, g, ld, in.refine_user);
+    if (in.local == 0) return;
+    std::vector<double*> dst(m);
+    for (size_t k = 0; k < m; ++k) dst[k] = a[k].get().data_wo();
+    if (rows_import_fn) {
+      check(rows_import_fn(in.dev->ctx(), g, ld, dst.data(), int(m), in.local), "ssp_rows_import");
+    } else {
+      for (size_t k = 0; k < m; ++k) check(ssp_copy(in.dev->ctx(), dst[k], g + k * ld, in.local), "ssp_copy");
+    }
+    return;
+  }
+  for (size_t k = 0; k < m; ++k)
+    check(ssp_download(in.dev->ctx(), p + k * ld + in.offset, x[k].get().data(), in.local), "ssp_download");
+  in.refine_fn(m, p, g, ld, in.refine_user);
+  for (size_t k = 0; k < m; ++k)
+    check(ssp_upload(in.dev->ctx(), a[k].get().data_wo(), g + k * ld + in.offset, in.local), "ssp_upload");
+}
+
+// Whether EndIteration returns its new parameter rows rounded to the Q storage format: the refined mode over
+// a Q space narrower than R (what solve() does before problem.action, solvers.h set_refine step 1).
+bool rounds_new_parameters(const Instance& in) { return in.solver->refine() && in.solver->q_bytes() < sizeof(double); }
+
+// solve() keeps the problem's diagonals in a Q vector; so does an instance whose Q space is narrower than R.
+// It matters: with actions stored rounded, the residual of a unit-vector guess is rounding noise (not an exact
+// zero) at the guess's index, and the default preconditioner divides it by (d - theta) + 1e-15 -- which must
+// then not be the exact zero the f64 diagonal would give.
+void store_diagonals_as_q(Instance& in) {
+  if (in.solver->q_bytes() < sizeof(double) && in.diagonals) in.solver->quantise(it::wrap_arg(*in.diagonals));
+}
+
+// Q_STORAGE, Q_REFINE, Q_REFINE_KAPPA of an options string (keys upper-cased by parse_options).
+struct QOptions {
+  bool f32 = false, refine = false, named = false;
+  double kappa = 8.0;
+};
+QOptions q_options(const char* options) {
+  QOptions q;
+  const auto m = it::parse_options(options ? options : "");
+  const it::util::StringFacet facet;
+  if (auto f = m.find("Q_STORAGE"); f != m.end()) {
+    const auto v = facet.tolower(f->second);
+    if (v != "f32" && v != "f64") throw std::invalid_argument("Q_STORAGE=" + f->second + ": must be f64 or f32");
+    q.f32 = v == "f32";
+    q.named = q.named || q.f32;
+  }
+  if (auto f = m.find("Q_REFINE"); f != m.end()) {
+    q.refine = facet.tobool(f->second);
+    q.named = q.named || q.refine;
+  }
+  if (auto f = m.find("Q_REFINE_KAPPA"); f != m.end()) {
+    if (!q.refine) throw std::invalid_argument("Q_REFINE_KAPPA: needs Q_REFINE=1");
+    q.kappa = std::stod(f->second);
+    if (!(q.kappa > 0)) throw std::invalid_argument("Q_REFINE_KAPPA=" + f->second + ": must be positive");
+  }
+  return q;
+}
+// The families that have neither option.
+void refuse_q_options(const char* options, const char* family) {
+  const auto q = q_options(options);
+  if (q.f32) throw std::invalid_argument(std::string("Q_STORAGE=f32: not available for ") + family);
+  if (q.refine) throw std::invalid_argument(std::string("Q_REFINE: not available for ") + family);
+}
+
+std::unique_ptr<itsolv_rc::RcSolver> face(std::unique_ptr<Solver> solver,
+                                          std::shared_ptr<it::ArrayHandlers<Vec, Vec, SparseP>> handlers) {
+  return std::make_unique<itsolv_rc::RcSolverOf<Vec>>(std::move(solver), std::move(handlers));
+}
 
 // add_vector on the staged R vectors (IterativeSolverAddVector and its device form).
 // Non-linear solvers take one vector through their own add_vector (for DIIS: the residual norm,
@@ -292,15 +413,33 @@ void IterativeSolverLinearEigensystemInitialize(size_t nQ, size_t nroot, size_t*
     (void)fname;
     Instance in;
     in.dev = make_device(fcomm);
+    const std::string method = algorithm ? algorithm : "";
+    const auto q = q_options(options);
+    if (q.named) {  // extension: the Q space in f32 and / or refined residuals, one-rank Davidson only
+      const char* which = q.f32 ? "Q_STORAGE=f32" : "Q_REFINE";
+      if (!(method == "Davidson" || method.empty()))
+        throw std::invalid_argument(std::string(which) + ": available for the LinearEigensystem Davidson only, not " + method);
+      if (in.dev->nranks() > 1)
+        throw std::invalid_argument(std::string(which) + ": not available on an instance with more than one rank");
+      if (q.f32 && !make_q32_fn)
+        throw std::logic_error("Q_STORAGE=f32: SSP_ERR_UNSUPPORTED: the loaded vector library has no mixed-precision ABI");
+    }
     // method dispatch and option parsing as the reference's create_LinearEigensystem (SolverFactory.h:114-125)
-    auto solver = it::create_LinearEigensystem(algorithm ? algorithm : "", options ? options : "",
-                                               molpro::linalg::hbm::make_handlers());
-    solver->set_n_roots(nroot);  // every method (reference IterativeSolverCMPI.cpp:176)
-    if (auto* d = dynamic_cast<Davidson*>(solver.get())) d->set_hermiticity(hermitian != 0);
-    solver->set_verbosity(verbosity_of(verbosity));
-    solver->set_convergence_threshold(thresh);
-    solver->set_convergence_threshold_value(thresh_value);
-    in.solver = std::move(solver);
+    if (q.f32) {  // the same construction over make_handlers_q32() (host_q32/rc_q32.cpp)
+      in.solver = make_q32_fn(options ? options : "", nroot, hermitian != 0);
+    } else {
+      auto handlers = molpro::linalg::hbm::make_handlers();
+      auto solver = it::create_LinearEigensystem(method, options ? options : "", handlers);
+      solver->set_n_roots(nroot);  // every method (reference IterativeSolverCMPI.cpp:176)
+      if (auto* d = dynamic_cast<Davidson*>(solver.get())) d->set_hermiticity(hermitian != 0);
+      in.solver = face(std::move(solver), std::move(handlers));
+    }
+    in.solver->set_verbosity(verbosity_of(verbosity));
+    in.solver->set_convergence_threshold(thresh);
+    in.solver->set_convergence_threshold_value(thresh_value);
+    // the refined mode's scope is checked here, not in the middle of a solve: hermitian = 0, MAX_SIZE_QSPACE,
+    // RESET_D and RESET_D_MAX_Q_SIZE are errors naming the option
+    if (q.refine) in.solver->set_refine(true, q.kappa);
     in.has_eigenvalues = true;
     setup(in, nQ, range_begin, range_end);
     push(std::move(in));
@@ -313,8 +452,9 @@ void IterativeSolverLinearEquationsInitialize(size_t n, size_t nroot, size_t* ra
                                               const char* algorithm, const char* options) {
   guarded([&] {
     (void)fname;
-    auto made = it::create_LinearEquations(algorithm ? algorithm : "", options ? options : "",
-                                           molpro::linalg::hbm::make_handlers());
+    refuse_q_options(options, "LinearEquations");
+    auto handlers = molpro::linalg::hbm::make_handlers();
+    auto made = it::create_LinearEquations(algorithm ? algorithm : "", options ? options : "", handlers);
     std::unique_ptr<LinEq> solver(static_cast<LinEq*>(made.release()));
     Instance in;
     in.dev = make_device(fcomm);
@@ -332,7 +472,7 @@ void IterativeSolverLinearEquationsInitialize(size_t n, size_t nroot, size_t* ra
     solver->set_convergence_threshold_value(thresh_value);
     if (aughes > 0) solver->set_augmented_hessian(aughes);
     solver->set_verbosity(verbosity_of(verbosity));
-    in.solver = std::move(solver);
+    in.solver = face(std::move(solver), std::move(handlers));
     push(std::move(in));
   });
 }
@@ -342,13 +482,14 @@ void IterativeSolverNonLinearEquationsInitialize(size_t n, size_t* range_begin, 
                                                  const char* algorithm, const char* options) {
   guarded([&] {
     (void)fname;
+    refuse_q_options(options, "NonLinearEquations");
     Instance in;
     in.dev = make_device(fcomm);
-    auto solver = it::create_NonLinearEquations(algorithm ? algorithm : "", options ? options : "",
-                                                molpro::linalg::hbm::make_handlers());
+    auto handlers = molpro::linalg::hbm::make_handlers();
+    auto solver = it::create_NonLinearEquations(algorithm ? algorithm : "", options ? options : "", handlers);
     solver->set_convergence_threshold(thresh);
     solver->set_verbosity(verbosity_of(verbosity));
-    in.solver = std::move(solver);
+    in.solver = face(std::move(solver), std::move(handlers));
     setup(in, n, range_begin, range_end);
     push(std::move(in));
   });
@@ -360,16 +501,17 @@ void IterativeSolverOptimizeInitialize(size_t n, size_t* range_begin, size_t* ra
   guarded([&] {
     (void)fname;
     (void)minimize;  // ignored, as the reference does (IterativeSolverCMPI.cpp:250-268)
+    refuse_q_options(options, "Optimize");
     Instance in;
     in.dev = make_device(fcomm);
-    auto solver = it::create_Optimize(algorithm ? algorithm : "", options ? options : "",
-                                      molpro::linalg::hbm::make_handlers());
+    auto handlers = molpro::linalg::hbm::make_handlers();
+    auto solver = it::create_Optimize(algorithm ? algorithm : "", options ? options : "", handlers);
     // reference IterativeSolverCMPI.cpp:245-264
     solver->set_n_roots(1);
     solver->set_convergence_threshold(thresh);
     solver->set_convergence_threshold_value(thresh_value);
     solver->set_verbosity(verbosity_of(verbosity));
-    in.solver = std::move(solver);
+    in.solver = face(std::move(solver), std::move(handlers));
     in.has_values = true;
     setup(in, n, range_begin, range_end);
     push(std::move(in));
@@ -399,6 +541,7 @@ size_t IterativeSolverAddVector(size_t buffer_size, double* parameters, double* 
     ensure_r(in, buffer_size);
     upload(in, in.rp, buffer_size, parameters);
     upload(in, in.ra, buffer_size, action);
+    const RefineScratch scratch(in, parameters, action, in.dimension, false);
     const size_t nwork = add_vector_staged(in, buffer_size);
     // The reference's R vectors are views of these host arrays, so every vector the solver wrote
     // (solutions and residuals of all roots, batch by batch) reaches the caller; sync gathers the
@@ -455,6 +598,7 @@ size_t IterativeSolverEndIteration(size_t buffer_size, double* solution, double*
     upload(in, in.rp, buffer_size, solution);
     upload(in, in.ra, buffer_size, residual);
     const size_t result = in.solver->end_iteration(first(in.rp, buffer_size), first(in.ra, buffer_size));
+    if (rounds_new_parameters(in)) in.solver->quantise(first(in.rp, std::min(result, buffer_size)));
     download(in, in.rp, buffer_size, solution);
     download(in, in.ra, buffer_size, residual);
     const size_t nws = std::min(in.solver->working_set().size(), buffer_size);
@@ -507,6 +651,7 @@ size_t IterativeSolverAddP(size_t buffer_size, size_t nP, const size_t* offsets,
         check(ssp_upload(I.dev->ctx(), act[k].get().data_wo(), host.data() + k * I.dimension + I.offset, I.local),
               "ssp_upload");
     };
+    const RefineScratch scratch(in, parameters, action, in.dimension, false);
     const size_t nwork =
         in.solver->add_p(it::cwrap(pvectors), ppm, first(in.rp, buffer_size), first(in.ra, buffer_size), apply);
     download(in, in.rp, buffer_size, parameters);
@@ -528,6 +673,7 @@ size_t IterativeSolverHbmAddVectorDevice(size_t buffer_size, double* parameters,
     ensure_r(in, buffer_size);
     import_rows(in, in.rp, buffer_size, parameters, ld);
     import_rows(in, in.ra, buffer_size, action, ld);
+    const RefineScratch scratch(in, parameters, action, ld, true);
     const size_t nwork = add_vector_staged(in, buffer_size);
     export_rows(in, in.rp, buffer_size, parameters, ld);
     export_rows(in, in.ra, buffer_size, action, ld);
@@ -570,7 +716,14 @@ size_t IterativeSolverHbmEndIterationDevice(size_t buffer_size, double* solution
     import_rows(in, in.rp, buffer_size, solution, ld);
     import_rows(in, in.ra, buffer_size, residual, ld);
     const size_t result = in.solver->end_iteration(first(in.rp, buffer_size), first(in.ra, buffer_size));
-    export_rows(in, in.rp, buffer_size, solution, ld);
+    // refined mode over an f32 Q space: the new parameter rows leave rounded, by the export itself where the
+    // library has the export that rounds, else by a pass over the staging vectors first (the same bits)
+    size_t mq = rounds_new_parameters(in) ? std::min(result, buffer_size) : 0;
+    if (mq > 0 && !rows_export_q_fn) {
+      in.solver->quantise(first(in.rp, mq));
+      mq = 0;
+    }
+    export_rows(in, in.rp, buffer_size, solution, ld, mq);
     export_rows(in, in.ra, buffer_size, residual, ld);
     return result;
   });
@@ -584,6 +737,7 @@ void IterativeSolverHbmSetDiagonalsDevice(const double* diagonals) {
     d.emplace_back(in.dev, in.dimension);
     import_rows(in, d, 1, diagonals, in.local);
     in.diagonals = std::make_unique<Vec>(std::move(d[0]));
+    store_diagonals_as_q(in);
   });
 }
 
@@ -606,25 +760,17 @@ void IterativeSolverErrors(double* errors) {
 
 void IterativeSolverEigenvalues(double* eigenvalues) {
   guarded([&] {
-    if (auto* d = dynamic_cast<Davidson*>(top().solver.get())) {
-      size_t k = 0;
-      for (double e : d->eigenvalues()) eigenvalues[k++] = e;
-    } else if (auto* r = dynamic_cast<RSPT*>(top().solver.get())) {
-      size_t k = 0;
-      for (double e : r->eigenvalues()) eigenvalues[k++] = e;
-    }
+    std::vector<double> ev;
+    if (!top().solver->eigenvalues(ev)) return;
+    std::copy(ev.begin(), ev.end(), eigenvalues);
   });
 }
 
 void IterativeSolverWorkingSetEigenvalues(double* eigenvalues) {
   guarded([&] {
-    if (auto* d = dynamic_cast<Davidson*>(top().solver.get())) {
-      size_t k = 0;
-      for (double e : d->working_set_eigenvalues()) eigenvalues[k++] = e;
-    } else if (auto* r = dynamic_cast<RSPT*>(top().solver.get())) {
-      size_t k = 0;
-      for (double e : r->working_set_eigenvalues()) eigenvalues[k++] = e;
-    }
+    std::vector<double> ev;
+    if (!top().solver->working_set_eigenvalues(ev)) return;
+    std::copy(ev.begin(), ev.end(), eigenvalues);
   });
 }
 
@@ -650,6 +796,7 @@ void IterativeSolverSetDiagonals(const double* diagonals) {
     auto& in = top();
     in.diagonals = std::make_unique<Vec>(in.dev, in.dimension);
     check(ssp_upload(in.dev->ctx(), in.diagonals->data_wo(), diagonals + in.offset, in.local), "ssp_upload");
+    store_diagonals_as_q(in);
   });
 }
 
@@ -723,6 +870,60 @@ int IterativeSolver_mpi_finalize(void) {
 }
 
 int IterativeSolverHbmMpiActive(void) { return active_mpi() ? 1 : 0; }
+
+// ---- the refined mode and the Q storage of the top instance (include/iterative_solver_c.h) ----------------
+int IterativeSolverHbmSetRefineAction(itsolv_refine_action_fn fn, void* user) {
+  return guarded([&] {
+    auto& in = top();
+    in.refine_fn = fn;
+    in.refine_user = user;
+    Instance* ip = &in;  // heap-held (instances)
+    if (fn) in.solver->set_refine_action([ip](const it::CVecRef<Vec>& x, const it::VecRef<Vec>& a) { refine_action(*ip, x, a); });
+    else in.solver->set_refine_action({});
+    return 0;
+  }) == 0 && g_error.empty() ? 0 : 1;
+}
+
+int IterativeSolverHbmRefineStatistics(int* refined_actions, int* first_refined_iteration, double* max_delta) {
+  if (instances.empty()) return 1;
+  const auto& s = *instances.back()->solver;
+  if (refined_actions) *refined_actions = s.refined_actions();
+  if (first_refined_iteration) *first_refined_iteration = s.first_refined_iteration();
+  if (max_delta) *max_delta = s.max_refine_delta();
+  return 0;
+}
+
+size_t IterativeSolverHbmQStorage(void) { return instances.empty() ? 0 : instances.back()->solver->q_bytes(); }
+
+size_t IterativeSolverHbmQuantise(size_t buffer_size, double* parameters) {
+  return guarded([&]() -> size_t {
+    auto& in = top();
+    if (in.solver->q_bytes() >= sizeof(double) || buffer_size == 0) return 0;
+    ensure_r(in, buffer_size);
+    upload(in, in.rp, buffer_size, parameters);
+    in.solver->quantise(first(in.rp, buffer_size));
+    download(in, in.rp, buffer_size, parameters);
+    return buffer_size;
+  });
+}
+
+size_t IterativeSolverHbmQuantiseDevice(size_t buffer_size, double* parameters, size_t ld) {
+  return guarded([&]() -> size_t {
+    auto& in = top();
+    if (in.solver->q_bytes() >= sizeof(double) || buffer_size == 0) return 0;
+    const bool have = rows_import_fn && rows_export_fn;
+    check_rows(in, buffer_size, parameters, ld, have, "IterativeSolverHbmQuantiseDevice");
+    ensure_r(in, buffer_size);
+    import_rows(in, in.rp, buffer_size, parameters, ld);
+    if (rows_export_q_fn) {
+      export_rows(in, in.rp, buffer_size, parameters, ld, buffer_size);
+    } else {
+      in.solver->quantise(first(in.rp, buffer_size));
+      export_rows(in, in.rp, buffer_size, parameters, ld);
+    }
+    return buffer_size;
+  });
+}
 
 int IterativeSolverHbmMpiAttach(ssp_ctx* ctx, int64_t fcomm, const char* transport) {
   return guarded([&] {

@@ -1,0 +1,143 @@
+// The Q-independent face of a solver behind the reverse-communication C API (iterative_solver_c.cpp).
+//
+// Everything the C layer calls on a solver takes R and P arguments only, so the instance holds this
+// interface instead of IterativeSolverTemplate<Vec, Vec, SparseP>: RcSolverOf<Q> implements it over a solver
+// with any Q.  Q = Vec is instantiated in host/; Q = VecF32 (Q_STORAGE=f32) in host_q32/, which host/ reaches
+// through the weak make_rc_davidson_q32 below -- null where host/ is linked without host_q32/ (the CPU
+// emulation of the f64 C ABI, which has no mixed-precision entry points).
+#pragma once
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "itsolv_hbm/hbm_handlers.h"
+#include "itsolv_hbm/solvers.h"
+
+namespace itsolv_rc {
+
+namespace it = molpro::linalg::itsolv;
+using molpro::linalg::hbm::SparseP;
+using molpro::linalg::hbm::Vec;
+
+class RcSolver {
+ public:
+  using fapply_on_p_type =
+      std::function<void(const std::vector<std::vector<double>>&, const it::CVecRef<SparseP>&, const it::VecRef<Vec>&)>;
+  using action_hook_type = std::function<void(const it::CVecRef<Vec>&, const it::VecRef<Vec>&)>;
+
+  virtual ~RcSolver() = default;
+  virtual bool nonlinear() const = 0;
+  virtual int add_vector(const it::VecRef<Vec>& parameters, const it::VecRef<Vec>& actions) = 0;
+  virtual int add_vector(Vec& parameters, Vec& actions, double value) = 0;
+  virtual size_t add_p(const it::CVecRef<SparseP>& pparams, const std::vector<double>& pp, const it::VecRef<Vec>& parameters,
+                       const it::VecRef<Vec>& actions, fapply_on_p_type apply_p) = 0;
+  virtual void solution(const std::vector<int>& roots, const it::VecRef<Vec>& parameters, const it::VecRef<Vec>& residual) = 0;
+  virtual size_t end_iteration(const it::VecRef<Vec>& parameters, const it::VecRef<Vec>& actions) = 0;
+  virtual bool end_iteration_needed() const = 0;
+  virtual const std::vector<int>& working_set() const = 0;
+  virtual size_t n_roots() const = 0;
+  virtual const std::vector<double>& errors() const = 0;
+  virtual const it::Statistics& statistics() const = 0;
+  virtual const it::subspace::Dimensions& dimensions() const = 0;
+  virtual double value() const = 0;
+  virtual void set_verbosity(it::Verbosity v) = 0;
+  virtual void set_convergence_threshold(double t) = 0;
+  virtual void set_convergence_threshold_value(double t) = 0;
+  virtual it::Verbosity get_verbosity() const = 0;
+  virtual int get_max_iter() const = 0;
+  virtual void set_max_iter(int n) = 0;
+  //! false for a solver without eigenvalues (nothing is written then)
+  virtual bool eigenvalues(std::vector<double>& out) const = 0;
+  virtual bool working_set_eigenvalues(std::vector<double>& out) const = 0;
+  // refined mode (itsolv_hbm/solvers.h set_refine)
+  virtual void set_refine(bool on, double kappa) = 0;  //!< also checks the mode's scope (errors name the option)
+  virtual bool refine() const = 0;
+  virtual void set_refine_action(action_hook_type hook) = 0;
+  virtual int refined_actions() const = 0;
+  virtual int first_refined_iteration() const = 0;
+  virtual double max_refine_delta() const = 0;
+  //! bytes per stored Q element
+  virtual size_t q_bytes() const = 0;
+  //! rounds the vectors to the Q storage format in place (nothing for a Q space stored as R)
+  virtual void quantise(const it::VecRef<Vec>& xx) = 0;
+};
+
+template <class Q>
+class RcSolverOf final : public RcSolver {
+  using Solver = it::IterativeSolverTemplate<Vec, Q, SparseP>;
+  using Handlers = std::shared_ptr<it::ArrayHandlers<Vec, Q, SparseP>>;
+
+ public:
+  RcSolverOf(std::unique_ptr<Solver> solver, Handlers handlers, size_t q_bytes = sizeof(double))
+      : m_s(std::move(solver)), m_h(std::move(handlers)), m_q_bytes(q_bytes) {}
+
+  bool nonlinear() const override { return m_s->nonlinear(); }
+  int add_vector(const it::VecRef<Vec>& p, const it::VecRef<Vec>& a) override { return m_s->add_vector(p, a); }
+  int add_vector(Vec& p, Vec& a, double value) override { return m_s->add_vector(p, a, value); }
+  size_t add_p(const it::CVecRef<SparseP>& pparams, const std::vector<double>& pp, const it::VecRef<Vec>& p,
+               const it::VecRef<Vec>& a, fapply_on_p_type apply_p) override {
+    return m_s->add_p(pparams, pp, p, a, std::move(apply_p));
+  }
+  void solution(const std::vector<int>& roots, const it::VecRef<Vec>& p, const it::VecRef<Vec>& r) override {
+    m_s->solution(roots, p, r);
+  }
+  size_t end_iteration(const it::VecRef<Vec>& p, const it::VecRef<Vec>& a) override { return m_s->end_iteration(p, a); }
+  bool end_iteration_needed() const override { return m_s->end_iteration_needed(); }
+  const std::vector<int>& working_set() const override { return m_s->working_set(); }
+  size_t n_roots() const override { return m_s->n_roots(); }
+  const std::vector<double>& errors() const override { return m_s->errors(); }
+  const it::Statistics& statistics() const override { return m_s->statistics(); }
+  const it::subspace::Dimensions& dimensions() const override { return m_s->dimensions(); }
+  double value() const override { return m_s->value(); }
+  void set_verbosity(it::Verbosity v) override { m_s->set_verbosity(v); }
+  void set_convergence_threshold(double t) override { m_s->set_convergence_threshold(t); }
+  void set_convergence_threshold_value(double t) override { m_s->set_convergence_threshold_value(t); }
+  it::Verbosity get_verbosity() const override { return m_s->get_verbosity(); }
+  int get_max_iter() const override { return m_s->get_max_iter(); }
+  void set_max_iter(int n) override { m_s->set_max_iter(n); }
+  bool eigenvalues(std::vector<double>& out) const override {
+    if (auto* d = dynamic_cast<const it::LinearEigensystemDavidson<Vec, Q, SparseP>*>(m_s.get())) out = d->eigenvalues();
+    else if (auto* r = dynamic_cast<const it::LinearEigensystemRSPT<Vec, Q, SparseP>*>(m_s.get())) out = r->eigenvalues();
+    else return false;
+    return true;
+  }
+  bool working_set_eigenvalues(std::vector<double>& out) const override {
+    if (!dynamic_cast<const it::LinearEigensystemDavidson<Vec, Q, SparseP>*>(m_s.get()) &&
+        !dynamic_cast<const it::LinearEigensystemRSPT<Vec, Q, SparseP>*>(m_s.get()))
+      return false;
+    out = m_s->working_set_eigenvalues();
+    return true;
+  }
+  void set_refine(bool on, double kappa) override {
+    if (on) m_s->validate_refine();
+    m_s->set_refine(on, kappa);
+  }
+  bool refine() const override { return m_s->refine(); }
+  void set_refine_action(action_hook_type hook) override { m_s->set_refine_action(std::move(hook)); }
+  int refined_actions() const override { return m_s->refined_actions(); }
+  int first_refined_iteration() const override { return m_s->first_refined_iteration(); }
+  double max_refine_delta() const override {
+    double d = 0;
+    for (double x : m_s->refine_delta()) d = std::max(d, x);
+    return d;
+  }
+  size_t q_bytes() const override { return m_q_bytes; }
+  void quantise(const it::VecRef<Vec>& xx) override {
+    using molpro::linalg::array::quantise_for_storage;
+    quantise_for_storage(m_h->qr(), xx);
+  }
+
+  Solver& solver() { return *m_s; }
+
+ private:
+  std::unique_ptr<Solver> m_s;
+  Handlers m_h;
+  size_t m_q_bytes;
+};
+
+// The hermitian-or-not LinearEigensystem "Davidson" over make_handlers_q32() (host_q32/rc_q32.cpp), options
+// parsed as create_LinearEigensystem parses them.  Weak: null without host_q32/.
+std::unique_ptr<RcSolver> make_rc_davidson_q32(const std::string& options, size_t nroot, bool hermitian)
+    __attribute__((weak));
+
+}  // namespace itsolv_rc

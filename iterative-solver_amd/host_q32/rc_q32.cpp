@@ -1,0 +1,21 @@
+// Q_STORAGE=f32 of the reverse-communication C API (include/iterative_solver_c.h): the instance's solver as
+// LinearEigensystemDavidson<Vec, VecF32, SparseP> over make_handlers_q32(), behind the Q-independent face of
+// host/rc_solver.h.  It lives here, not in host/, for the reason host_q32/itsolv_q32.cpp does: the handlers
+// call the mixed-precision C ABI, which the CPU emulation that host/ is also linked against does not have.
+#include "../host/rc_solver.h"
+#include "itsolv_hbm/hbm_handlers_f32.h"
+#include "itsolv_hbm/solver_factory.h"
+
+namespace itsolv_rc {
+
+std::unique_ptr<RcSolver> make_rc_davidson_q32(const std::string& options, size_t nroot, bool hermitian) {
+  using molpro::linalg::hbm::VecF32;
+  auto handlers = molpro::linalg::hbm::make_handlers_q32();
+  auto solver = it::create_LinearEigensystem("Davidson", options, handlers);
+  solver->set_n_roots(nroot);
+  if (auto* d = dynamic_cast<it::LinearEigensystemDavidson<Vec, VecF32, SparseP>*>(solver.get()))
+    d->set_hermiticity(hermitian);
+  return std::make_unique<RcSolverOf<VecF32>>(std::move(solver), std::move(handlers), sizeof(float));
+}
+
+}  // namespace itsolv_rc

@@ -444,8 +444,9 @@ class IterativeSolverTemplate {
   //     of a batch in one call -- converged roots included, since the solver recomputes every root's residual
   //     in every iteration.  That is the price of actions stored in 4 bytes.
   // Scope: the hermitian LinearEigensystemDavidson, no max_size_qspace, reset_D or reset_D_max_Q_size, an
-  // empty D space (each is an error naming the option), and solve() only: add_vector called by hand has no
-  // action to refine with and throws.
+  // empty D space (each is an error naming the option).  The refined residuals need the problem's action:
+  // solve() provides it; a caller driving add_vector by hand gives it with set_refine_action, and rounds the
+  // parameter vectors itself before it applies the action (step 1).  Without either, a needed refinement throws.
   void set_refine(bool on, double kappa = 8.0) {
     m_xspace->set_refined(on);
     m_refine = on;
@@ -460,6 +461,12 @@ class IterativeSolverTemplate {
   int refined_actions() const { return m_refined_actions; }
   int first_refined_iteration() const { return m_first_refined_iteration; }
   const std::vector<double>& refine_delta() const { return m_refine_delta; }
+  //! The action the refined residuals are formed with: actions[k] = H parameters[k].  It stays until it is
+  //! replaced or cleared (an empty hook); solve() uses the problem's action for its duration and restores it.
+  using action_hook_type = std::function<void(const CVecRef<R>&, const VecRef<R>&)>;
+  void set_refine_action(action_hook_type hook) { m_action_hook = std::move(hook); }
+  //! Throws unless this solver, as it is set up now, supports the refined mode (what set_refine's scope names).
+  void validate_refine() const { check_refine(); }
 
   //! The current settings (reference IterativeSolverTemplate.h:262-267; derived solvers add theirs).
   virtual std::shared_ptr<Options> get_options() const {
@@ -486,8 +493,9 @@ class IterativeSolverTemplate {
     // refined mode: the solver reaches the problem's action for the refined residuals while solve() runs
     struct HookScope {
       action_hook_type& hook;
-      ~HookScope() { hook = nullptr; }
-    } hook_scope{m_action_hook};
+      action_hook_type callers;  // set_refine_action's: restored on every way out
+      ~HookScope() { hook = std::move(callers); }
+    } hook_scope{m_action_hook, m_action_hook};
     if (m_refine) {
       check_refine();
       m_action_hook = [&problem](const CVecRef<R>& x, const VecRef<R>& a) { problem.action(x, a); };
@@ -629,8 +637,6 @@ class IterativeSolverTemplate {
     return m_working_set.size();
   }
 
-  using action_hook_type = std::function<void(const CVecRef<R>&, const VecRef<R>&)>;
-
   //! Throws unless this solver, as it is set up, supports the refined mode (set_refine).
   virtual void check_refine() const {
     throw std::logic_error("refine: available for the hermitian LinearEigensystemDavidson only");
@@ -646,7 +652,9 @@ class IterativeSolverTemplate {
     if (d.nQ == 0) return;  // nothing is stored rounded yet
     if (d.nD != 0) throw std::runtime_error("refine: a D space is not supported");
     if (!m_action_hook)
-      throw std::logic_error("refine: needs the problem's action, which only solve() provides (not add_vector by hand)");
+      throw std::logic_error(
+          "refine: needs the problem's action, which only solve() provides (not add_vector by hand) unless "
+          "set_refine_action has given it (C API: IterativeSolverHbmSetRefineAction)");
     check_refine();
     const auto& norms = m_xspace->q_action_norms();
     const auto& sol = m_subspace_solver->solutions();
@@ -710,7 +718,7 @@ class IterativeSolverTemplate {
   // refined mode (set_refine)
   bool m_refine = false;
   double m_refine_kappa = 8.0;
-  action_hook_type m_action_hook{};  // problem.action, set by solve() for its duration
+  action_hook_type m_action_hook{};  // set_refine_action's; problem.action while solve() runs
   int m_refined_actions = 0;
   int m_first_refined_iteration = 0;  // 0: none yet
   std::vector<double> m_refine_delta;

@@ -37,6 +37,16 @@ DEVICE_SIG = {
     "IterativeSolverHbmSetDiagonalsDevice": (None, [P]),
     "IterativeSolverHbmDiagonalsDevice": (None, [P]),
 }
+# The Q space in f32 and the refined residuals (Q_STORAGE / Q_REFINE options of LinearEigensystem): declared
+# only when the loaded library has them, and a set of their own (DEVICE_SIG stays the device forms).
+REFINE_ACTION = C.CFUNCTYPE(None, Z, P, P, Z, P)
+REFINE_SIG = {
+    "IterativeSolverHbmSetRefineAction": (I, [REFINE_ACTION, P]),
+    "IterativeSolverHbmRefineStatistics": (I, [PI, PI, PD]),
+    "IterativeSolverHbmQStorage": (Z, []),
+    "IterativeSolverHbmQuantise": (Z, [Z, PD]),
+    "IterativeSolverHbmQuantiseDevice": (Z, [Z, P, Z]),
+}
 _ctx = None  # the context given to use_context
 
 
@@ -89,7 +99,7 @@ def _load():
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
             f.restype, f.argtypes = res, args
-        for name, (res, args) in DEVICE_SIG.items():  # declared only when the loaded library has them
+        for name, (res, args) in {**DEVICE_SIG, **REFINE_SIG}.items():  # declared only when the library has them
             f = getattr(lib, name, None)
             if f is not None:
                 f.restype, f.argtypes = res, args
@@ -126,6 +136,21 @@ def _dcall(name, *args):
     if not hasattr(_load(), name):
         raise RuntimeError(f"{name}: the loaded library has no device forms of the reverse-communication calls")
     return _call(name, *args)
+
+
+def _rcall(name, *args):
+    if not hasattr(_load(), name):
+        raise RuntimeError(f"{name}: the loaded library has no refined mode of the reverse-communication calls")
+    return _call(name, *args)
+
+
+def _option(options, key):
+    """The value of `key` in a "k1=v1,k2=v2" options string (keys case-insensitive), or None."""
+    for field in options.replace(";", ",").split(","):
+        k, sep, v = field.replace(":", "=", 1).partition("=")
+        if sep and k.strip().upper() == key:
+            return v.strip()
+    return None
 
 
 def _is_device(a):
@@ -226,10 +251,74 @@ class IterativeSolver:
     def add_vector(self, parameters, action, sync=True):
         self._check_top()
         dev = _device_pair(self, parameters, action)
+        self._refine_ctx = parameters.ctx if dev is not None else None  # where a refine action's arrays live
         if dev is not None:
-            return int(_dcall("IterativeSolverHbmAddVectorDevice", *dev))
+            r = int(_dcall("IterativeSolverHbmAddVectorDevice", *dev))
+        else:
+            nbuffer = parameters.shape[0] if parameters.ndim > 1 else 1
+            r = int(_call("IterativeSolverAddVector", nbuffer, _d(_flat(parameters)), _d(_flat(action)), int(sync)))
+        self._reraise_refine()
+        return r
+
+    # -- the Q space in f32 and refined residuals (options Q_STORAGE=f32, Q_REFINE=1 of LinearEigensystem) ----
+    def set_refine_action(self, fn):
+        """The action the refined mode forms its residuals with: fn(parameters, action) sets action[k] =
+        H parameters[k].  Called from inside add_vector / add_p with numpy views of shape (m, n) of that call's
+        own arrays, or, for a call on device arrays, with DeviceRows of m rows and the call's ld.  None clears."""
+        self._check_top()
+        if fn is None:
+            _rcall("IterativeSolverHbmSetRefineAction", REFINE_ACTION(), None)
+            self._refine_tramp = None
+            return
+
+        def tramp(nvec, p, g, ld, user):
+            try:
+                ctx = getattr(self, "_refine_ctx", None)
+                if ctx is not None:
+                    from subspace_hip import DeviceRows
+
+                    fn(DeviceRows(ctx, nvec, self.local, ld, ptr=p), DeviceRows(ctx, nvec, self.local, ld, ptr=g))
+                else:
+                    x = np.ctypeslib.as_array((C.c_double * (nvec * ld)).from_address(p)).reshape(nvec, ld)
+                    a = np.ctypeslib.as_array((C.c_double * (nvec * ld)).from_address(g)).reshape(nvec, ld)
+                    fn(x, a)
+            except BaseException as e:  # noqa: BLE001 - cannot unwind through the C layer: raised by the caller
+                self._refine_exc = e
+
+        tr = REFINE_ACTION(tramp)
+        _rcall("IterativeSolverHbmSetRefineAction", tr, None)
+        self._refine_tramp = tr  # keep alive for the solver's lifetime
+
+    def _reraise_refine(self):
+        e, self._refine_exc = getattr(self, "_refine_exc", None), None
+        if e is not None:
+            raise e
+
+    def quantise(self, parameters):
+        """Rounds parameter rows in place to the instance's Q storage format (nothing with Q_STORAGE=f64): what an
+        initial guess that is not a unit vector needs before its action is formed in refined mode.  Returns
+        the number of rows rounded."""
+        self._check_top()
+        if _is_device(parameters):
+            if parameters.n != self.local:
+                raise ValueError(f"device rows hold this rank's range of {self.local} elements, not {parameters.n}")
+            return int(_rcall("IterativeSolverHbmQuantiseDevice", getattr(parameters, "m", 1), parameters.ptr,
+                              getattr(parameters, "ld", parameters.n)))
         nbuffer = parameters.shape[0] if parameters.ndim > 1 else 1
-        return int(_call("IterativeSolverAddVector", nbuffer, _d(_flat(parameters)), _d(_flat(action)), int(sync)))
+        return int(_rcall("IterativeSolverHbmQuantise", nbuffer, _d(_flat(parameters))))
+
+    @property
+    def q_storage(self):
+        """Bytes per stored Q element: 8, or 4 with Q_STORAGE=f32."""
+        self._check_top()
+        return int(_rcall("IterativeSolverHbmQStorage"))
+
+    def refine_statistics(self):
+        self._check_top()
+        n, first, delta = C.c_int(), C.c_int(), C.c_double()
+        if _rcall("IterativeSolverHbmRefineStatistics", C.byref(n), C.byref(first), C.byref(delta)) != 0:
+            raise RuntimeError("no active solver")
+        return {"refined_actions": n.value, "first_refined_iteration": first.value, "max_delta": delta.value}
 
     def add_value(self, value, parameters, action, sync=True):
         self._check_top()
@@ -276,8 +365,11 @@ class IterativeSolver:
 
         self._apply_p = APPLY_P(tramp)  # keep alive for the solver's lifetime
         nbuffer = parameters.shape[0] if parameters.ndim > 1 else 1
-        return int(_call("IterativeSolverAddP", nbuffer, nP, offsets.ctypes.data_as(PZ), idx.ctypes.data_as(PZ),
-                         _d(coef), _d(ppm), _d(_flat(parameters)), _d(_flat(action)), int(sync), self._apply_p))
+        self._refine_ctx = None
+        r = int(_call("IterativeSolverAddP", nbuffer, nP, offsets.ctypes.data_as(PZ), idx.ctypes.data_as(PZ),
+                      _d(coef), _d(ppm), _d(_flat(parameters)), _d(_flat(action)), int(sync), self._apply_p))
+        self._reraise_refine()
+        return r
 
     @property
     def end_iteration_needed(self):
@@ -334,6 +426,9 @@ class IterativeSolver:
                     parameters[i, i] = 1
         nwork = nbuffer
         value = None
+        if getattr(self, "_refines", False):  # refined mode: the problem's action forms the refined residuals,
+            self.set_refine_action(problem.action)  # and the guess is rounded to what the Q space will store
+            self.quantise(parameters)
         for it in range(_call("IterativeSolverMaxIter")):
             if _call("IterativeSolverNonLinear") > 0:
                 value = problem.residual(parameters.reshape([parameters.shape[-1]]),
@@ -408,6 +503,9 @@ class IterativeSolver:
                 ctx.sparse_copy(parameters.row(i), guess[i:i + 1], [1.0] * len(guess[i:i + 1]), offset=self.offset)
         nwork = nbuffer
         value = None
+        if getattr(self, "_refines", False):  # as the host loop
+            self.set_refine_action(problem.action)
+            self.quantise(parameters)
         for it in range(_call("IterativeSolverMaxIter")):
             if _call("IterativeSolverNonLinear") > 0:
                 value = problem.residual(parameters.row(0), actions.row(0))
@@ -475,6 +573,8 @@ class LinearEigensystem(IterativeSolver):
         self._register_range(rb, re)
         if range is not None:
             range[0], range[1] = rb.value, re.value
+        # solve() gives the refined mode (Q_REFINE=1) the problem's action and a rounded initial guess
+        self._refines = (_option(options, "Q_REFINE") or "0").upper() in ("1", "T", "TRUE")
 
     @property
     def eigenvalues(self):

@@ -58,6 +58,8 @@ EXPORTS = [
     "ssp_quantise_f32",
     # a caller's row-major block of vectors into and out of library vectors, device to device
     "ssp_rows_import", "ssp_rows_export",
+    # the export that rounds its first rows through f32 (the refined f32 Q space of the RC API)
+    "ssp_rows_export_quantised",
 ]
 
 # The mixed-precision entry points are optional in a loaded library: the CPU emulation of the f64 C ABI
@@ -72,6 +74,8 @@ OPTIONAL_Q32 = frozenset(n for n in EXPORTS if n.startswith("ssp_q32_"))
 # The row-block entry points (a caller's device block <-> library vectors), optional in the same way and a
 # set of their own: the three sets above stay what they were.
 OPTIONAL_ROWS = frozenset({"ssp_rows_import", "ssp_rows_export"})
+# The export that rounds, optional in the same way; again a set of its own.
+OPTIONAL_ROWS_Q = frozenset({"ssp_rows_export_quantised"})
 SSP_F64, SSP_F32 = 0, 1
 
 
@@ -203,8 +207,9 @@ def _declare(lib):
         "ssp_q32_block_update": (I, [P, PD, PZ, PZ, PD, I, PD, P, I, P, PD, I, Z, Z]),
         "ssp_rows_import": (I, [P, P, Z, P, I, Z]),
         "ssp_rows_export": (I, [P, P, PD, I, P, Z, Z]),
+        "ssp_rows_export_quantised": (I, [P, P, PD, I, I, P, Z, Z]),
     }
-    optional = OPTIONAL | OPTIONAL_Q32 | OPTIONAL_REFINED | OPTIONAL_ROWS
+    optional = OPTIONAL | OPTIONAL_Q32 | OPTIONAL_REFINED | OPTIONAL_ROWS | OPTIONAL_ROWS_Q
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -919,6 +924,16 @@ class Context:
             raise ValueError("rows_export: one vector of the rows' length per row")
         a = None if xs is None else self._scales(xs, len(src))
         _check(f(self.handle, _ptrs(src), None if a is None else _dptr(a), len(src), rows.ptr, rows.ld, rows.n))
+
+    def rows_export_quantised(self, src: Sequence[DeviceVector], rows: DeviceRows, xs=None, mq=None):
+        """rows_export with the first mq rows (None: all) rounded through float32 as they are stored:
+        row k = float64(float32(xs[k] * src[k])) for k < mq (ssp_rows_export_quantised)."""
+        f = self._rows("ssp_rows_export_quantised")
+        if len(src) > rows.m or any(v.n != rows.n for v in src):
+            raise ValueError("rows_export_quantised: one vector of the rows' length per row")
+        a = None if xs is None else self._scales(xs, len(src))
+        mq = len(src) if mq is None else int(mq)
+        _check(f(self.handle, _ptrs(src), None if a is None else _dptr(a), len(src), mq, rows.ptr, rows.ld, rows.n))
 
     # -- fused solver passes over an f32 Q space (include/subspace_hip.h ssp_q32_*) -----------------
     def q32_gemm_inner_cols(self, rows, cols, xs=None, ys=None) -> np.ndarray:

@@ -10,7 +10,14 @@
 Everything runs in one process; every figure is the median of `--reps` samples after discarded warm-ups, each
 sample a host clock around work that ends in a stream synchronisation.
 
+With --options (repeatable, `OPTIONS[@THRESHOLD]`, "" for none) the tool measures the f32 Q space behind the API
+instead: ssp_rows_export_quantised beside the scaled ssp_rows_export, and the device-route solve once per option
+set -- wall per iteration, iterations, refined actions, ssp_memory_stats bytes in use at the end.  An option set
+with Q_REFINE gets the synthetic action as its refine action and runs without the C3 Q-space limit (the refined
+mode has no D space).
+
 usage: python tools/device_api_cost.py [--out profiles/r11/device_api.md] [--reps 11] [--quick]
+       python tools/device_api_cost.py --options "" --options Q_STORAGE=f32@1e-6 --options Q_STORAGE=f32,Q_REFINE=1@1e-8
 """
 import argparse
 import os
@@ -85,14 +92,45 @@ def rows_table(ctx, sizes, reps):
     return lines
 
 
-def api_solve(ctx, n, device, max_iter):
-    """One Davidson solve through the reverse-communication loop; returns per-phase wall times."""
+def rows_q_table(ctx, sizes, reps):
+    """ssp_rows_export_quantised with mq = m beside ssp_rows_export scaled, aligned rows, same process."""
+    lines = ["| N | m | rows_export, scaled | rows_export_q, mq = m | q / plain |", "|---|---|---|---|---|"]
+    for n in sizes:
+        for m in (8, 16):
+            vecs = [ctx.alloc(n) for _ in range(m)]
+            buf = ctx.alloc(m * n)
+            for k, v in enumerate(vecs):
+                ctx.fill_random(v, 3, k)
+            rows = sh.DeviceRows(ctx, m, n, n, ptr=buf.ptr)
+            xs = [0.75] * m
+            t = median_ms(ctx, [lambda: ctx.rows_export(vecs, rows, xs), lambda: ctx.rows_export_quantised(vecs, rows, xs, m)],
+                          reps)
+            tb = [16.0 * m * n / (1e9 * x) for x in t]
+            lines.append(f"| {n:.0e} | {m} | {t[0]:.3f} ms, {tb[0]:.2f} TB/s | {t[1]:.3f} ms, {tb[1]:.2f} TB/s | {t[1] / t[0]:.3f} |")
+            print(lines[-1], flush=True)
+            for v in vecs + [buf]:
+                v.free()
+            ctx.release_cached()
+    return lines
+
+
+def api_solve(ctx, n, device, max_iter, options=None, thresh=None):
+    """One Davidson solve through the reverse-communication loop; returns per-phase wall times.  options: an
+    option set of --options (None: the C3 options of the r11 report)."""
     nroot = C3["nroots"]
-    s = iterative_solver.LinearEigensystem(n, nroot, thresh=C3["convergence_threshold"], thresh_value=BIG, hermitian=True,
-                                           options=f"MAX_SIZE_QSPACE={C3['max_size_qspace']},RESET_D={C3['reset_D']}")
+    limits = f"MAX_SIZE_QSPACE={C3['max_size_qspace']},RESET_D={C3['reset_D']}"
+    refines = options is not None and "Q_REFINE=1" in options.upper().replace(" ", "")
+    full = limits if options is None else options if refines else ",".join(x for x in (limits, options) if x)
+    s = iterative_solver.LinearEigensystem(n, nroot, thresh=thresh or C3["convergence_threshold"], thresh_value=BIG,
+                                           hermitian=True, options=full)
+    if refines:  # device rows in, device rows out
+        s.set_refine_action(lambda x, a: ctx.synthetic_action(x.rows(), a.rows(), C3["rho"], C3["rank"], C3["seed"]))
     px, pg = sh.DeviceRows(ctx, nroot, n), sh.DeviceRows(ctx, nroot, n)
     diag = ctx.alloc(n)
     ctx.synthetic_diagonal(diag, C3["rho"], C3["rank"])
+    if options is not None:  # the diagonals as the instance keeps them: in Q storage (rounded for an f32 Q space)
+        iterative_solver._dcall("IterativeSolverHbmSetDiagonalsDevice", diag.ptr)
+        iterative_solver._dcall("IterativeSolverHbmDiagonalsDevice", diag.ptr)
     if device:
         x, g = px, pg
         for k in range(nroot):
@@ -143,8 +181,10 @@ def api_solve(ctx, n, device, max_iter):
     led = ctx.ledger()
     ctx.ledger_enable(False)
     rows_ms = sum(led[k]["ms"] for k in ("rows_import", "rows_export") if k in led)
+    rows_ms += sum(v["ms"] for k, v in led.items() if k.startswith("rows_export_q"))
     out = dict(iterations=iters, wall=wall, api=t_api, action=t_action, rows_ms=rows_ms, errors=float(np.max(s.errors)),
-               eigenvalue=float(s.eigenvalues[0]))
+               eigenvalue=float(s.eigenvalues[0]), refined_actions=s.refine_statistics()["refined_actions"],
+               bytes_in_use=ctx.memory_stats()[0], q_storage=s.q_storage)
     s.finalize()
     for v in (px, pg, diag):
         v.free()
@@ -181,8 +221,34 @@ def solve_table(ctx, n, reps, max_iter):
     return lines
 
 
+def options_table(ctx, n, reps, max_iter, option_sets):
+    """The device-route solve once per option set of --options."""
+    iterative_solver.use_context(ctx)
+    runs = {o: [] for o in option_sets}
+    for rep in range(1 + reps):  # the first of each is a warm-up
+        for o in option_sets:
+            opts, _, thresh = o.partition("@")
+            rec = api_solve(ctx, n, True, max_iter, opts, float(thresh) if thresh else None)
+            if rep > 0:
+                runs[o].append(rec)
+            print(o or "(none)", rec, flush=True)
+    iterative_solver.use_context(None)
+    lines = ["| options @ threshold | Q bytes per element | iterations | wall per iteration | inside the API calls, per iteration | "
+             "refined actions | largest error at the end | bytes in use at the end | lowest eigenvalue |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    for o, recs in runs.items():
+        med = lambda key: statistics.median(r[key] / r["iterations"] for r in recs)  # noqa: E731
+        r0 = recs[0]
+        lines.append(f"| `{o or '(none)'}` | {r0['q_storage']} | {r0['iterations']} | {1e3 * med('wall'):.1f} ms | "
+                     f"{1e3 * med('api'):.1f} ms | {r0['refined_actions']} | {r0['errors']:.2e} | {r0['bytes_in_use']} | "
+                     f"{r0['eigenvalue']:.12f} |")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--options", action="append", default=None, metavar="OPTIONS[@THRESHOLD]",
+                    help="measure the f32 Q space behind the API: one device-route solve per option set (repeatable)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r11", "device_api.md"))
     ap.add_argument("--reps", type=int, default=11)
     ap.add_argument("--solve-reps", type=int, default=3)
@@ -194,6 +260,26 @@ def main():
     ctx = sh.Context(0)
     sizes = (10**5,) if a.quick else (10**7, 10**8)
     n_solve = 10**5 if a.quick else 10**7
+    if a.options is not None:
+        out = a.out if a.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "r12", "rc_q32_tables.md")
+        doc = ["# The f32 Q space behind the reverse-communication API: measured", "",
+               f"`tools/device_api_cost.py --reps {a.reps} --solve-reps {a.solve_reps} " +
+               " ".join(f'--options "{o}"' for o in a.options) + "`" + (" --quick (REHEARSAL SIZES)" if a.quick else "") +
+               ", one process on one MI355X; medians after discarded warm-ups.", "",
+               "## ssp_rows_export_quantised beside ssp_rows_export", "", "Bytes are 16 m N, aligned rows, scale 0.75.", ""]
+        doc += rows_q_table(ctx, sizes, a.reps)
+        doc += ["", f"## Device-route solve, C3 at N = {n_solve:.0e} (8 roots, rank-8 problem, no P space)", "",
+                f"Median of {a.solve_reps} solves after one warm-up solve each.  Option sets without Q_REFINE run with the C3 "
+                f"limits MAX_SIZE_QSPACE={C3['max_size_qspace']},RESET_D={C3['reset_D']}; one with Q_REFINE runs without "
+                "them (the refined mode has no D space).", ""]
+        doc += options_table(ctx, n_solve, a.solve_reps, a.max_iter, a.options)
+        ctx.close()
+        text = "\n".join(doc) + "\n"
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text)
+        print(text)
+        return
     doc = ["# Device forms of the reverse-communication API: measured cost", "",
            f"`tools/device_api_cost.py --reps {a.reps} --solve-reps {a.solve_reps}`" + (" --quick (REHEARSAL SIZES)" if a.quick else "") +
            ", one process on one MI355X.  Medians of the samples after discarded warm-ups; every sample is a host "
