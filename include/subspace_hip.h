@@ -155,7 +155,27 @@ int ssp_ledger_entry(ssp_ctx* ctx, int i, const char** name, long long* calls, d
  * view) must stay allocated until a call that stores or drops the fill -- any call other than the
  * exceptions above, ssp_ctx_stream or ssp_synchronize -- has returned; blocks of ssp_alloc are safe,
  * ssp_free drops their fills.
- * SSP_DEFER_FILL=0 in the environment at ssp_ctx_create: every fill is launched at once. */
+ * SSP_DEFER_FILL=0 in the environment at ssp_ctx_create: every fill is launched at once.
+ *
+ * Deferred gemm_outer.  A write-only gemm_outer -- ssp_gemm_outer_set[_scaled], or ssp_gemm_outer[_scaled]
+ * that ran as one over deferred vectors (above) -- with every scale 1.0, at most 64 sources and 16
+ * destinations and vectors longer than the short-vector limit is validated at once but launched LATER:
+ * by the next entry point of the context, whichever it is, before that entry point does anything else.
+ * Errors of the arguments are reported by the call itself, a failure of the launch by the call that
+ * launches it.  The one exception: an ssp_axpy (or ssp_axpy_scaled with both scales 1.0) whose y is
+ * exactly one of the pending destinations (same address and length), that has no such axpy yet, and
+ * whose x shares no byte with any pending destination (it may be one of the sources), with
+ * sources + destinations <= 64.  It launches nothing: the pending launch adds alpha * x to that
+ * destination's finished sum before storing it, by the fma the axpy itself would have applied to the
+ * stored value, so the results are the same bits with one read and one write of y less (the residual
+ * update r_i -= lambda_i x_i after construct_solution).  It is the same contract as for deferred fills:
+ * every library call sees the memory the immediate launches would have left; code that touches device
+ * memory WITHOUT a library call must take ssp_ctx_stream or call ssp_synchronize first, and the
+ * operands (x of an attached axpy included) must stay allocated until a later call of the context has
+ * returned; ssp_free launches the pending gemm_outer before the block returns to the arena, and
+ * ssp_ctx_destroy discards it.  In the ledger the launch is a "gemm_outer" / "gemm_outer_set" row of
+ * 8 n (k + m + e) bytes for e attached terms, which have no "axpy" row.
+ * SSP_DEFER_OUTER=0 in the environment at ssp_ctx_create: every gemm_outer is launched at once. */
 int ssp_fill(ssp_ctx* ctx, double alpha, double* x, size_t n);
 /* x[:] *= alpha                        reference ArrayHandlerIterable.h:54-57 */
 int ssp_scal(ssp_ctx* ctx, double alpha, double* x, size_t n);

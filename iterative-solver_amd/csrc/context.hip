@@ -52,6 +52,7 @@ int use_device(ssp_ctx* ctx) {
 
 int enter(ssp_ctx* ctx) {
   SSP_TRY(use_device(ctx));
+  SSP_TRY(flush_outer(ctx));
   return flush_fills(ctx);
 }
 
@@ -482,6 +483,7 @@ int ssp_ctx_create(int device, ssp_ctx** out) {
   }
   if (const char* sm = std::getenv("SSP_SYNTH_MERGE")) ctx->synth_merge = std::atoi(sm) != 0;
   if (const char* df = std::getenv("SSP_DEFER_FILL")) ctx->defer_fill = std::atoi(df) != 0;
+  if (const char* dout = std::getenv("SSP_DEFER_OUTER")) ctx->defer_outer = std::atoi(dout) != 0;
   if (const char* ct = std::getenv("SSP_COMM_TIMEOUT_S")) {
     const double v = std::atof(ct);
     if (v > 0) ctx->comm_timeout_s = v;
@@ -510,6 +512,7 @@ int ssp_ctx_destroy(ssp_ctx* ctx) {
   if (!ctx) return SSP_OK;
   (void)hipSetDevice(ctx->device);
   ctx->pending_fills.clear();  // nobody can read the vectors of a destroyed context
+  ctx->pending_outer.discard();
   (void)ssp::p2p_detach(ctx);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->comm) ncclCommDestroy(ctx->comm);
@@ -543,7 +546,8 @@ int ssp_ctx_destroy(ssp_ctx* ctx) {
 }
 
 // The hand-off of the stream to foreign code: work the caller queues on it may read any vector, so
-// every pending zero fill is stored first (ssp_last_error keeps a failure to launch one).
+// the pending gemm_outer is launched and every pending zero fill stored first (ssp_last_error keeps a
+// failure to launch one).
 void* ssp_ctx_stream(ssp_ctx* ctx) {
   if (!ctx) return nullptr;
   (void)ssp::enter(ctx);

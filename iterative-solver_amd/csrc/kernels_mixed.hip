@@ -642,6 +642,7 @@ namespace ssp {
 // sources (k_mx_outer; the destination scales ride along with the first source chunk).
 int q32_dense_pass(ssp_ctx* ctx, const double* alphas, const float* const* xx, int k, double* const* yy,
                    const double* ys, int m, size_t n, bool set) {
+  SSP_TRY(flush_outer(ctx));  // this pass keeps zero fills pending, never a recorded gemm_outer
   if (set && k == 0) {  // zero fills that may stay deferred, as ssp_gemm_outer_set's
     for (int j = 0; j < m; ++j) SSP_TRY(ssp_fill(ctx, 0.0, yy[j], n));
     return SSP_OK;

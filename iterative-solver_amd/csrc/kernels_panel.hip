@@ -346,12 +346,19 @@ struct OuterArgs {
   int k;
   int m;
   int set;  // 1: yy[j] = sum (destinations not read: fill(0) + gemm_outer in one pass)
+  // EPI: bit j set: y[j] += epi[j] * x[k + j] (the epilogue sources ride in the source slots past the
+  // k sources, so k + m <= kOuterSrc).  The new members sit in the padding after `set` and behind
+  // `alpha`: every other member keeps its offset, and the instances without EPI their code.
+  int epi_mask;
   size_t n;
   const double* alpha_dev;         // k*m > kOuterAlpha: alpha[i*m + j] in device memory
   const double* scale_dev;         // SC: deferred scales, sources [0, k) then destinations [k, k + m)
   double alpha[ssp::kOuterAlpha];  // alpha[i*m + j] in the argument block
+  double epi[ssp::kOuterDst];
 };
 static_assert(sizeof(OuterArgs) <= 4000, "kernel argument block too large");
+static_assert(ssp::PendingOuter::kSrc == ssp::kOuterSrc && ssp::PendingOuter::kDst == ssp::kOuterDst,
+              "pending_outer.h records one launch");
 
 // yy[j] += sum_i alpha(i,j) xx[i]: for each destination the sources are added in order i = 0..k-1,
 // as the reference's pairwise axpy loop does (util/gemm.h:259-264).  Each wave owns windows of
@@ -365,8 +372,13 @@ constexpr int kOuterWin = 4;
 // own name in rocprofv3 statistics, so its launches are not averaged with the read-modify-write ones.
 // SC: sources and (read-modify-write) destinations with deferred scales, applied as each element is
 // loaded (include/subspace_hip.h ssp_gemm_outer_scaled).
-template <int M, bool DEV, bool SET, bool SC = false>
+// EPI (the flushed record of pending_outer.h with attached ssp_axpy terms): before destination j of
+// a.epi_mask is stored, epi[j] * x[k + j] is added to its finished sum by the fma k_axpy_win would have
+// done on the stored value.  Unmasked destinations take no term: fma(0, x, acc) would turn a -0.0 sum
+// into +0.0 and an infinite x into NaN.
+template <int M, bool DEV, bool SET, bool SC = false, bool EPI = false>
 __global__ __launch_bounds__(kBlock) void k_gemm_outer(const OuterArgs a) {
+  static_assert(!EPI || (SET && !SC), "the epilogue rides on the unscaled write-only form");
   using ssp::ld2nt;
   using ssp::st2nt;
   // Device-resident alphas are read through the constant address space (scalar loads, as the
@@ -444,6 +456,36 @@ __global__ __launch_bounds__(kBlock) void k_gemm_outer(const OuterArgs a) {
         }
       }
     }
+    if constexpr (EPI) {
+      // B destinations' terms in flight.  The compiler gives ev registers of its own beside xv's (16 B
+      // VGPRs at U = 4), so B is what keeps each instance at the waves per SIMD of its write-only form:
+      // two at M = 8 (234 VGPRs, two waves, 8 loads per lane in flight), one elsewhere.
+      constexpr int B = M == 8 ? 2 : 1;
+#pragma unroll
+      for (int j0 = 0; j0 < M; j0 += B) {
+        double2 ev[B][U];
+        bool on[B];
+#pragma unroll
+        for (int b = 0; b < B; ++b) {
+          on[b] = j0 + b < a.m && ((a.epi_mask >> (j0 + b)) & 1);
+          if (on[b]) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) ev[b][u] = ok[u] ? ld2nt(a.x[a.k + j0 + b] + 2 * (p0 + 64 * u)) : z2;
+          }
+        }
+#pragma unroll
+        for (int b = 0; b < B; ++b) {
+          if (on[b]) {
+            const double ea = a.epi[j0 + b];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+              acc[u][j0 + b].x = fma(ea, ev[b][u].x, acc[u][j0 + b].x);
+              acc[u][j0 + b].y = fma(ea, ev[b][u].y, acc[u][j0 + b].y);
+            }
+          }
+        }
+      }
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u)
       if (ok[u])
@@ -456,6 +498,9 @@ __global__ __launch_bounds__(kBlock) void k_gemm_outer(const OuterArgs a) {
     const int j = threadIdx.x;
     double v = SET ? 0.0 : sc1<SC>(a.y[j][e], scale(a.k + j));
     for (int i = 0; i < a.k; ++i) v = fma(alpha(i * a.m + j), sc1<SC>(a.x[i][e], scale(i)), v);
+    if constexpr (EPI) {
+      if ((a.epi_mask >> j) & 1) v = fma(a.epi[j], a.x[a.k + j][e], v);
+    }
     a.y[j][e] = v;
   }
 }
@@ -1263,18 +1308,18 @@ int launch_inner(ssp_ctx* ctx, const InnerArgs& a, unsigned grid, bool sc, bool 
   return sc ? launch_inner_sc<true>(ctx, a, grid, pre) : launch_inner_sc<false>(ctx, a, grid, pre);
 }
 
-template <bool DEV, bool SET, bool SC>
+template <bool DEV, bool SET, bool SC, bool EPI = false>
 void launch_outer_t(ssp_ctx* ctx, unsigned grid, const OuterArgs& a) {
   if (a.m <= 1)
-    SSP_LAUNCH((k_gemm_outer<1, DEV, SET, SC>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
+    SSP_LAUNCH((k_gemm_outer<1, DEV, SET, SC, EPI>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
   else if (a.m <= 2)
-    SSP_LAUNCH((k_gemm_outer<2, DEV, SET, SC>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
+    SSP_LAUNCH((k_gemm_outer<2, DEV, SET, SC, EPI>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
   else if (a.m <= 4)
-    SSP_LAUNCH((k_gemm_outer<4, DEV, SET, SC>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
+    SSP_LAUNCH((k_gemm_outer<4, DEV, SET, SC, EPI>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
   else if (a.m <= 8)
-    SSP_LAUNCH((k_gemm_outer<8, DEV, SET, SC>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
+    SSP_LAUNCH((k_gemm_outer<8, DEV, SET, SC, EPI>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
   else
-    SSP_LAUNCH((k_gemm_outer<16, DEV, SET, SC>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
+    SSP_LAUNCH((k_gemm_outer<16, DEV, SET, SC, EPI>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
 }
 
 template <bool SC>
@@ -1288,6 +1333,14 @@ void launch_outer_sc(ssp_ctx* ctx, unsigned grid, const OuterArgs& a) {
 int launch_outer(ssp_ctx* ctx, const OuterArgs& a) {
   // workgroups per CU of the launch: ctx->outer_per_cu (SSP_OUTER_WG_PER_CU at context creation)
   const unsigned grid = ssp::stream_grid(ctx, a.n / 2 + 1, kOuterWin, unsigned(ctx->outer_per_cu));
+  if (a.epi_mask) {  // a flushed record with ssp_axpy terms: write-only, unscaled, its epilogue sources in place
+    if (!a.set || a.scale_dev || a.k + a.m > ssp::kOuterSrc)
+      return ssp::set_error(SSP_ERR_ARG, "gemm_outer: epilogue terms on a launch that cannot carry them");
+    a.alpha_dev ? launch_outer_t<true, true, false, true>(ctx, grid, a)
+                : launch_outer_t<false, true, false, true>(ctx, grid, a);
+    SSP_TRY_HIP(hipGetLastError());
+    return SSP_OK;
+  }
   a.scale_dev ? launch_outer_sc<true>(ctx, grid, a) : launch_outer_sc<false>(ctx, grid, a);
   SSP_TRY_HIP(hipGetLastError());
   return SSP_OK;
@@ -1487,6 +1540,54 @@ int ssp_gemm_inner_scaled(ssp_ctx* ctx, const double* const* xx, const double* x
 }  // extern "C"
 
 namespace {
+// The launch of a flushed record (pending_outer.h): the write-only kernel its call would have launched,
+// or with attached terms its EPI instantiation, under the call's own ledger row; each term adds one
+// source stream to the row's bytes.
+int launch_record(ssp_ctx* ctx, const ssp::PendingOuter::Record& r) {
+  const int e = r.terms();
+  ssp::LedgerScope ls(ctx, r.set ? "gemm_outer_set" : "gemm_outer", 8.0 * r.n * (r.k + r.m + e));
+  OuterArgs a{};
+  a.k = r.k;
+  a.m = r.m;
+  a.set = 1;
+  a.n = r.n;
+  for (int i = 0; i < r.k; ++i) a.x[i] = r.x[i];
+  for (int j = 0; j < r.m; ++j) a.y[j] = r.y[j];
+  if (e > 0) {  // attach() has checked that the epilogue sources fit behind the k sources
+    a.epi_mask = int(r.mask);
+    for (int j = 0; j < r.m; ++j) {
+      const bool on = (r.mask >> j) & 1u;
+      a.x[r.k + j] = on ? r.ex[j] : nullptr;
+      a.epi[j] = on ? r.ea[j] : 0.0;
+    }
+  }
+  const bool dev = r.k * r.m > ssp::kOuterAlpha;
+  if (dev) {
+    void* p;
+    SSP_TRY(ssp::upload_small(ctx, r.alpha, size_t(r.k) * r.m * sizeof(double), &p));
+    a.alpha_dev = static_cast<const double*>(p);
+    SSP_TRY(ssp::flush_uploads(ctx));
+  } else {
+    std::copy(r.alpha, r.alpha + r.k * r.m, a.alpha);
+  }
+  const int mi = a.m <= 1 ? 1 : a.m <= 2 ? 2 : a.m <= 4 ? 4 : a.m <= 8 ? 8 : 16;
+  std::string tag = shape_tag(dev ? "dev" : "arg", mi, a.set, a.k, a.m, false);
+  if (e > 0) tag += " epi" + std::to_string(e);
+  ls.detail(tag);
+  return launch_outer(ctx, a);
+}
+}  // namespace
+
+namespace ssp {
+int flush_outer(ssp_ctx* ctx) {
+  if (!ctx->pending_outer.pending()) return SSP_OK;
+  int status = SSP_OK;
+  ctx->pending_outer.flush([&](const PendingOuter::Record& r) { status = launch_record(ctx, r); });
+  return status;
+}
+}  // namespace ssp
+
+namespace {
 int gemm_outer_impl(ssp_ctx* ctx, const double* alphas, const double* const* xx, const double* xs, int k,
                     double* const* yy, const double* ys, int m, size_t n, bool set) {
   SSP_CHECK_CTX_KEEP_FILLS(ctx);
@@ -1537,6 +1638,13 @@ int gemm_outer_impl(ssp_ctx* ctx, const double* alphas, const double* const* xx,
     }
   }
   const bool set0 = set || consume;  // the destinations are not read by their first launch
+  // Deferred gemm_outer (pending_outer.h): the unscaled write-only form of one launch is recorded, not
+  // launched, so that the ssp_axpy calls that follow on its destinations ride on its stores; whatever
+  // else comes next launches it first (ssp::flush_outer, under this call's ledger row).  Everything
+  // above has happened as for the launch, so no pending zero fill overlaps an operand of the record.
+  if (ctx->defer_outer && set0 && !any_scaled(xs, k) && !ssp::exact_mode(ctx, n) &&
+      ctx->pending_outer.record(alphas, xx, k, yy, m, n, set))
+    return SSP_OK;
   // Destinations are independent; sources are applied in increasing order, in groups that fit
   // the kernel argument block, so each destination sees the reference's summation order.
   ssp::LedgerScope ls(ctx, set ? "gemm_outer_set" : "gemm_outer", 8.0 * n * (k + (set0 ? 1.0 : 2.0) * m));

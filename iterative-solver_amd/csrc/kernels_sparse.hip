@@ -675,7 +675,8 @@ int solution_impl(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const 
   SSP_TRY(dense());
   if (uidx.empty()) return SSP_OK;
   // with no dense source the write-only pass above is m deferred zero fills: the fix-up below writes
-  // into those vectors, so they are stored first
+  // into those vectors, so they are stored first; so is a dense pass that was recorded (pending_outer.h)
+  SSP_TRY(ssp::flush_outer(ctx));
   SSP_TRY(ssp::flush_fills(ctx));
   ConstructFixArgs<TX> a{};
   unsigned long long *dptr, *dli;

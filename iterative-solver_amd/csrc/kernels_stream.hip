@@ -455,11 +455,21 @@ int copy_impl(ssp_ctx* ctx, double alpha, double* x, const double* y, size_t n, 
 
 int axpy_impl(ssp_ctx* ctx, double alpha, const double* x, double xs, double* y, double ys, size_t n,
               const char* what) {
-  SSP_CHECK_CTX(ctx);
+  SSP_CHECK_CTX_KEEP_ALL(ctx);
+  const bool sc = xs != 1.0 || ys != 1.0;
+  // Deferred gemm_outer (pending_outer.h): an unscaled axpy onto exactly one destination of the pending
+  // record becomes its epilogue term and launches nothing; x is read by that launch, so its pending
+  // zero fills are stored first.  Any other axpy launches the record, and stores every fill, as the
+  // default prologue does.
+  if (ctx->pending_outer.pending()) {
+    const bool valid = n > 0 && x && y && ssp::aligned16(x) && ssp::aligned16(y);
+    if (valid && !sc && ctx->pending_outer.attach(alpha, x, y, n)) return ssp::flush_fills_over(ctx, x, n);
+    SSP_TRY(ssp::flush_outer(ctx));
+  }
+  SSP_TRY(ssp::flush_fills(ctx));
   SSP_TRY(check_vec(x, n, what));
   SSP_TRY(check_vec(y, n, what));
   if (n == 0) return SSP_OK;
-  const bool sc = xs != 1.0 || ys != 1.0;
   ssp::LedgerScope ls(ctx, "axpy", 24.0 * n);
   if (ssp::exact_mode(ctx, n)) return ssp::exact_outer(ctx, &alpha, &x, &xs, 1, &y, &ys, 1, n, false);
   if (n >= kWinMin) {

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "pending_fill.h"
+#include "pending_outer.h"
 #include "subspace_hip.h"
 
 // Per-operation ledger: HIP events bracket each hot-path kernel on the context's stream, with the
@@ -56,6 +57,11 @@ struct ssp_ctx {
   // at once (the same-build A/B, and the eager side of tests/test_deferred_fill_gpu.py).
   bool defer_fill = true;
   ssp::PendingFills pending_fills;
+  // A write-only gemm_outer of one launch recorded instead of launched, so that the ssp_axpy calls on
+  // its destinations ride on its stores (pending_outer.h); SSP_DEFER_OUTER=0: launched at once (the
+  // same-build A/B, and the eager side of tests/test_deferred_outer_gpu.py).
+  bool defer_outer = true;
+  ssp::PendingOuter pending_outer;
   hipStream_t stream = nullptr;
 
   // HBM arena: freed blocks are kept by rounded size and recycled (Q vectors are created and
@@ -160,7 +166,10 @@ int fill_now(ssp_ctx* ctx, double alpha, double* x, size_t n);
 int flush_fills(ssp_ctx* ctx);
 int flush_fills_over(ssp_ctx* ctx, const void* p, size_t n);
 int overwrite_fills(ssp_ctx* ctx, const void* p, size_t n);
-// use_device, then flush_fills.
+// Deferred gemm_outer (kernels_panel.hip): launches the context's pending record, if there is one, under
+// its "gemm_outer" / "gemm_outer_set" ledger row.
+int flush_outer(ssp_ctx* ctx);
+// use_device, then flush_outer and flush_fills.
 int enter(ssp_ctx* ctx);
 int ensure_partial(ssp_ctx* ctx, size_t n_doubles);
 int ensure_result(ssp_ctx* ctx, size_t n_doubles);
@@ -508,18 +517,27 @@ int launch_reduce_partials(ssp_ctx* ctx, const double* partial, int nblocks, int
     if (_s != SSP_OK) return _s;   \
   } while (0)
 
-// Prologue of every entry point: the context's device made current and every pending zero fill
-// stored, so that whatever the entry point launches or copies sees the memory an eager fill would
-// have left (nothing that touched a pending range ran since its ssp_fill).
+// Prologue of every entry point: the context's device made current, the pending gemm_outer launched
+// and every pending zero fill stored, so that whatever the entry point launches or copies sees the
+// memory the eager calls would have left (nothing that touched a pending range ran since its call).
 #define SSP_CHECK_CTX(ctx)                                              \
   do {                                                                  \
     if (!(ctx)) return ssp::set_error(SSP_ERR_ARG, "null ssp_ctx");     \
     SSP_TRY(ssp::enter(ctx));                                           \
   } while (0)
 
-// The same without the flush, for the entry points that look at the table themselves: ssp_fill,
-// ssp_gemm_outer*, ssp_copy, ssp_scal_copy and ssp_free.
+// The same with the zero fills left pending (the pending gemm_outer is launched), for the entry points
+// that look at the table themselves: ssp_fill, ssp_gemm_outer*, ssp_copy, ssp_scal_copy, ssp_rows_* and
+// ssp_free.
 #define SSP_CHECK_CTX_KEEP_FILLS(ctx)                                   \
+  do {                                                                  \
+    if (!(ctx)) return ssp::set_error(SSP_ERR_ARG, "null ssp_ctx");     \
+    SSP_TRY(ssp::use_device(ctx));                                      \
+    SSP_TRY(ssp::flush_outer(ctx));                                     \
+  } while (0)
+
+// Device only: ssp_axpy, which may attach to the pending gemm_outer instead of launching it.
+#define SSP_CHECK_CTX_KEEP_ALL(ctx)                                     \
   do {                                                                  \
     if (!(ctx)) return ssp::set_error(SSP_ERR_ARG, "null ssp_ctx");     \
     SSP_TRY(ssp::use_device(ctx));                                      \

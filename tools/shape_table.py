@@ -22,9 +22,11 @@ GROUPS = [
     (r"^gemm_inner \[mfma-pre<2,(\d+)> .* sc\]", lambda m: rf"^k_gemm_inner<2, {m.group(1)}, false, true, \w+, true>"),
     (r"^gemm_inner \[sym<2,2> 8x8\]", lambda m: r"^k_gemm_inner<2, 2, true, false"),
     (r"^gemm_inner \[sym<2,2> 8x8 sc\]", lambda m: r"^k_gemm_inner<2, 2, true, true"),
-    (r"^gemm_outer_set \[arg<8,1> \d+x8 sc\]", lambda m: r"^k_gemm_outer<8, false, true, true>"),
-    (r"^gemm_outer_set \[arg<8,1> \d+x8\]", lambda m: r"^k_gemm_outer<8, false, true, false>"),
-    (r"^gemm_outer \[arg<8,0> \d+x8 sc\]", lambda m: r"^k_gemm_outer<8, false, false, true>"),
+    # (traces from before the EPI parameter of k_gemm_outer name four template arguments)
+    (r"^gemm_outer_set \[arg<8,1> \d+x8 sc\]", lambda m: r"^k_gemm_outer<8, false, true, true(, false)?>"),
+    (r"^gemm_outer_set \[arg<8,1> \d+x8\]", lambda m: r"^k_gemm_outer<8, false, true, false(, false)?>"),
+    (r"^gemm_outer_set \[arg<8,1> \d+x8 epi\d+\]", lambda m: r"^k_gemm_outer<8, false, true, false, true>"),
+    (r"^gemm_outer \[arg<8,0> \d+x8 sc\]", lambda m: r"^k_gemm_outer<8, false, false, true(, false)?>"),
     (r"^transform_gram \[transform<8,2> 8x8 sc\]", lambda m: r"^k_transform<8, 2, true>"),
     (r"^transform_gram \[transform<8,1> 8x8\]", lambda m: r"^k_transform<8, 1, true>"),
     (r"^axpy_pairs_norm$", lambda m: r"^k_axpy_pairs_norm"),
