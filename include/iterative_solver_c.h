@@ -180,11 +180,26 @@ void IterativeSolverHbmDiagonalsDevice(double* diagonals);
  *                   reaches f64 thresholds (1e-10).  Allowed with Q_STORAGE=f64 too: nothing is rounded there
  *                   (delta = 0), and the only effect is that a root is declared converged on the residual of
  *                   its solution's own action.
+ *   Q_REFINE_DSPACE=1  (needs Q_REFINE=1; refused by name without it) the refined mode under a Q-space limit:
+ *                   MAX_SIZE_QSPACE is then allowed, and whenever the limit deletes Q vectors the D space is
+ *                   rebuilt consistently (itsolv_hbm/solvers.h set_refine_dspace): new D parameters from the
+ *                   stored parameters alone, rounded once, and TRUE actions of exactly those vectors, which the
+ *                   refine action supplies -- nD <= nroot more actions per rebuild, in one call.  The rebuild
+ *                   happens inside IterativeSolverEndIteration and its device form, whose two arrays are free as
+ *                   scratch once imported: the refine action is called there with rows [0, nD) of them, under
+ *                   the contract below.  RESET_D and RESET_D_MAX_Q_SIZE stay refused.
+ *                   A rebuild cuts the Q space somewhat below the limit, so that rebuilds (each rounds the D
+ *                   parameters once more) do not come in every iteration: by two working sets where that is
+ *                   under a quarter of the limit, else by one, else not at all.  Q_REFINE_DSPACE_SLACK=<n>
+ *                   (needs Q_REFINE_DSPACE=1; n >= 0) sets the number of vectors instead; 0 is the schedule of
+ *                   the plain solver, a rebuild in every iteration once the Q space is full.  With a limit under
+ *                   about 8 nroot the mode may stall short of an f64 threshold (near 1e-10 |H|).
  * Refused, each with an error that names the option (recorded, not thrown, after IterativeSolverHbmSetThrow(0)):
  * an unknown Q_STORAGE value; either option on LinearEquations, NonLinearEquations, Optimize or RSPT; either
  * option on an instance with more than one rank; Q_REFINE with hermitian = 0, MAX_SIZE_QSPACE, RESET_D or
  * RESET_D_MAX_Q_SIZE (the refined mode has no D space); Q_STORAGE=f32 over a vector library without the
- * mixed-precision ABI.  Out of scope: multi-rank f32 instances, a D space or a Q-space limit in refined mode,
+ * mixed-precision ABI.  Out of scope: multi-rank f32 instances, a D space or a Q-space limit in refined mode
+ * without Q_REFINE_DSPACE=1, the D-space reset in refined mode,
  * f32 Q for the other solver families, a Fortran binding of the refine callback (the Fortran module passes
  * `options` through, so the plain Q_STORAGE=f32 works from Fortran), a device-side apply_on_p.
  *
@@ -220,6 +235,9 @@ int IterativeSolverHbmSetRefineAction(itsolv_refine_action_fn fn, void* user);
 /* Of the top instance: actions spent on refined residuals, the iteration (from 1) of the first (0: none), the
  * largest delta (the bound on |estimate - true residual|) of the last iteration.  Returns 0; 1: no instance. */
 int IterativeSolverHbmRefineStatistics(int* refined_actions, int* first_refined_iteration, double* max_delta);
+/* Of the top instance with Q_REFINE_DSPACE=1: the rebuilds of its D space and the actions spent on them (these
+ * are not among the refined_actions above).  Returns 0; 1: no instance. */
+int IterativeSolverHbmRefineDspaceStats(int* rebuilds, int* actions);
 /* Bytes per stored Q element of the top instance: 8 or 4; 0 when there is none. */
 size_t IterativeSolverHbmQStorage(void);
 /* Rounds `buffer_size` parameter rows in place to the Q storage format of the top instance (host rows of

@@ -145,6 +145,32 @@ int itsolv_davidson_synth_q32_refined(ssp_ctx* ctx, size_t n, const sspx_synth* 
  * pointer may be NULL.  Returns 0. */
 int itsolv_q32_refine_stats(int* refined_actions, int* first_refined_iteration, double* max_delta);
 
+/* The refined mode UNDER A Q-SPACE LIMIT (itsolv_hbm/solvers.h set_refine_dspace): the two refined solves with
+ * max_size_qspace admitted.  Whenever the limit deletes Q vectors the D space is rebuilt consistently:
+ *   - the new D parameters are written by one pass over the parameters of the deleted Q vectors and of the old
+ *     D space (ssp_q32_combine_widen: each the f64 sum of its sources, rounded once, with the stored value
+ *     widened beside it); the stored Q / D actions are not read and nothing is rescaled after the rounding;
+ *   - the D actions are TRUE actions of exactly those stored vectors, one action call for all of them;
+ *   - the D blocks of S and H come from these in f64, and the bound delta_i gains the D terms
+ *     2^-24 sum_d |c_di| |a_d|.
+ * The price: nD <= nroots more actions per rebuild.  What a rebuild cannot keep is the part of the solutions
+ * that the rounding of the new D parameters removes from the subspace (2^-24 of each element), which later
+ * iterations restore at the solver's convergence rate; so a rebuild cuts the Q space up to two working sets
+ * BELOW max_size_qspace (never a quarter of it; nothing where the limit is below about 8 nroots) and the next
+ * comes two or three iterations later.  Where nothing is cut every iteration rebuilds, and thresholds within a
+ * small multiple of 2^-24 |H - lambda| |tail of the solution| are out of reach.
+ * Scope: as the refined entries, with max_size_qspace allowed; reset_D and an explicit reset_D_max_Q_size
+ * stay refused.  Same arguments as the refined entries. */
+int itsolv_davidson_dense_q32_refined_dspace(ssp_ctx* ctx, const double* h, size_t n, const itsolv_options* opt,
+                                             const itsolv_q32_refine* refine, itsolv_result* out,
+                                             double* solutions_out);
+int itsolv_davidson_synth_q32_refined_dspace(ssp_ctx* ctx, size_t n, const sspx_synth* spec, const itsolv_options* opt,
+                                             const itsolv_q32_refine* refine, itsolv_result* out,
+                                             double* solutions_out);
+/* What the calling thread's last such solve spent on its D space: rebuilds, and the actions on them (these
+ * are not among itsolv_q32_refine_stats' refined_actions).  Any pointer may be NULL.  Returns 0. */
+int itsolv_q32_dspace_stats(int* rebuilds, int* actions);
+
 /* DIIS on r(x) = H (x - 1) for a dense row-major H (reference test_NonLinearEquations.cpp:38-49). */
 /* LinearEquationsDavidson (reference itsolv/LinearEquationsDavidson.h): A x_r = b_r for nrhs
  * right-hand sides b (row-major nrhs x n, host), dense row-major A resident in HBM (single rank).

@@ -406,6 +406,19 @@ int ssp_q32_construct_solution(ssp_ctx* ctx, const double* palphas, const size_t
 int ssp_q32_block_update(ssp_ctx* ctx, const double* palphas, const size_t* ptr, const size_t* idx, const double* val,
                          int kp, const double* alphas, const float* const* xx, int k, double* const* yy,
                          const double* ys, int m, size_t n, size_t offset);
+/* New f32 vectors as combinations of existing ones, with their f64 twins (the consistent D space of the
+ * refined f32 Q space, itsolv_hbm/solvers.h set_refine_dspace):
+ *   yy[j][:] = (float)(sum_i alphas[i*m + j] xx[i][:])   the f64 sum of the sources in order, rounded once
+ *   ww[j][:] = (double)yy[j][:]                            the stored value, widened
+ * in one pass that reads the k sources once and reads neither destination set.  Both outputs are bit-identical
+ * to ssp_mx_gemm_outer(F32 -> F32, set = 1) followed by ssp_mx_copy(ww[j], SSP_F64, yy[j], SSP_F32, 1.0), at
+ * every length and in exact mode (on vectors of at most exact_max elements: the exact path of
+ * ssp_mx_gemm_outer, then the widening copies); with more than 64 sources the launches chain as
+ * ssp_mx_gemm_outer's do and the last one writes the twins.  Pending zero fills of the destinations are
+ * dropped, those of the sources stored.  No destination may alias a source or another destination; k = 0
+ * writes zeros; m = 0 and n = 0 return at once.  Ledger name combine_widen_f32, bytes n (4 k + 12 m). */
+int ssp_q32_combine_widen(ssp_ctx* ctx, const double* alphas, const float* const* xx, int k, float* const* yy,
+                          double* const* ww, int m, size_t n);
 
 /* ---- selection: reference util/select.h:28-55, util/select_max_dot.h:166-190,
  *      DistrArray.cpp:170-276.  Local shard [offset, offset+n) of a global array.  Returns up

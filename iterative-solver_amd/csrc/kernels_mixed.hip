@@ -12,8 +12,8 @@
 // kernel moves 512 N.
 //
 // Kernels.  k_mx_copy, k_mx_axpy, k_mx_scal, k_mx_dot: one per-element operation each, over map_quads;
-// k_quantise_f32 (f64 vectors rounded through f32 in place, up to 16 per launch); k_mx_fill; k_mx_outer<TX, TY, M, SET> (gemm_outer, launched chunk by chunk from outer_chunks, also the
-// dense pass of the ssp_q32_* updates); k_mx_inner<TX, CP, MG, NG> (gemm_inner: the one MFMA tile kernel,
+// k_quantise_f32 (f64 vectors rounded through f32 in place, up to 16 per launch); k_mx_fill; k_mx_outer<TX, TY, M, SET, TWIN> (gemm_outer, launched chunk by chunk from outer_chunks, also the
+// dense pass of the ssp_q32_* updates; TWIN: ssp_q32_combine_widen's second store of every result, widened); k_mx_inner<TX, CP, MG, NG> (gemm_inner: the one MFMA tile kernel,
 // CP the columns' storage -- float, double, or ByGroup for ssp_q32_gemm_inner_cols).  with_pair maps the
 // storage pair of a call to the kernel's types.
 #include <algorithm>
@@ -222,6 +222,7 @@ __global__ __launch_bounds__(kBlock) void k_quantise_f32(const QuantArgs a) {
 struct MxOuterArgs {
   const void* x[ssp::kOuterSrc];
   void* y[ssp::kOuterDst];
+  double* w[ssp::kOuterDst];  // TWIN only: the f64 twins of the f32 destinations
   int k;
   int m;
   size_t n;
@@ -239,8 +240,12 @@ static_assert(sizeof(MxOuterArgs) <= 4000, "kernel argument block too large");
 // once, as it is stored.  Alphas and scales are wave-uniform reads through the constant address space.
 // A destination's scale (the launch of a call's first source chunk only) is applied as the destination
 // is loaded, acc = y * ys[j]: the rounding an eager scal stores, as k_gemm_outer's SC form does.
-template <typename TX, typename TY, int M, bool SET>
+// TWIN (f32 destinations; ssp_q32_combine_widen, the launch of a call's last source chunk only): each
+// accumulator is stored twice, rounded to y[j] and that rounded value widened to w[j] -- the f64 quad's two
+// 16-byte stores beside the f32 quad's one, what k_mx_copy<double, float> would store from y[j] read back.
+template <typename TX, typename TY, int M, bool SET, bool TWIN = false>
 __global__ __launch_bounds__(kBlock) void k_mx_outer(const MxOuterArgs a) {
+  static_assert(!TWIN || sizeof(TY) == 4, "a twin belongs to an f32 destination");
   using cdouble = const __attribute__((address_space(4))) double;
   using cchar = const __attribute__((address_space(4))) char;
   cdouble* const alpha = a.alpha_dev ? (cdouble*)a.alpha_dev
@@ -321,7 +326,14 @@ __global__ __launch_bounds__(kBlock) void k_mx_outer(const MxOuterArgs a) {
       if (ok[u])
 #pragma unroll
         for (int j = 0; j < M; ++j)
-          if (j < a.m) stq<true>(static_cast<TY*>(a.y[j]) + 4 * (p0 + 64 * u), acc[u][j]);
+          if (j < a.m) {
+            stq<true>(static_cast<TY*>(a.y[j]) + 4 * (p0 + 64 * u), acc[u][j]);
+            if constexpr (TWIN) {
+              const double r[4] = {double(float(acc[u][j][0])), double(float(acc[u][j][1])), double(float(acc[u][j][2])),
+                                   double(float(acc[u][j][3]))};
+              stq<true>(a.w[j] + 4 * (p0 + 64 * u), r);
+            }
+          }
   }
   // the n mod 4 last elements: thread j of workgroup 0 owns destination j
   if ((a.n & 3) && blockIdx.x == 0 && int(threadIdx.x) < a.m) {
@@ -332,6 +344,7 @@ __global__ __launch_bounds__(kBlock) void k_mx_outer(const MxOuterArgs a) {
       if (yscale_p) v *= yscale_p[j];
       for (int i = 0; i < a.k; ++i) v = fma(alpha[i * a.m + j], double(static_cast<const TX*>(a.x[i])[e]) * scale(i), v);
       y[e] = TY(v);
+      if constexpr (TWIN) a.w[j][e] = double(TY(v));
     }
   }
 }
@@ -579,22 +592,24 @@ unsigned inner_grid(const ssp_ctx* ctx, size_t n) {
   return unsigned(std::max<size_t>(1, std::min(blocks, cap)));
 }
 
-template <typename TX, typename TY, bool SET>
+template <typename TX, typename TY, bool SET, bool TWIN = false>
 void launch_outer_m(ssp_ctx* ctx, unsigned grid, const MxOuterArgs& a) {
   const dim3 g(grid), b(kBlock);
-  if (a.m <= 1) SSP_LAUNCH((k_mx_outer<TX, TY, 1, SET>), g, b, 0, ctx->stream, a);
-  else if (a.m <= 2) SSP_LAUNCH((k_mx_outer<TX, TY, 2, SET>), g, b, 0, ctx->stream, a);
-  else if (a.m <= 4) SSP_LAUNCH((k_mx_outer<TX, TY, 4, SET>), g, b, 0, ctx->stream, a);
-  else if (a.m <= 8) SSP_LAUNCH((k_mx_outer<TX, TY, 8, SET>), g, b, 0, ctx->stream, a);
-  else SSP_LAUNCH((k_mx_outer<TX, TY, 16, SET>), g, b, 0, ctx->stream, a);
+  if (a.m <= 1) SSP_LAUNCH((k_mx_outer<TX, TY, 1, SET, TWIN>), g, b, 0, ctx->stream, a);
+  else if (a.m <= 2) SSP_LAUNCH((k_mx_outer<TX, TY, 2, SET, TWIN>), g, b, 0, ctx->stream, a);
+  else if (a.m <= 4) SSP_LAUNCH((k_mx_outer<TX, TY, 4, SET, TWIN>), g, b, 0, ctx->stream, a);
+  else if (a.m <= 8) SSP_LAUNCH((k_mx_outer<TX, TY, 8, SET, TWIN>), g, b, 0, ctx->stream, a);
+  else SSP_LAUNCH((k_mx_outer<TX, TY, 16, SET, TWIN>), g, b, 0, ctx->stream, a);
 }
 
 // yy[j] = (set ? 0 : ys[j] yy[j]) + sum_i alphas(i, j) (xs[i] xx[i]) on the bandwidth path (k, m, n > 0).
 // Destinations are independent, kOuterDst per launch; sources are applied in increasing order, kOuterSrc per
 // launch, so each destination sees the reference's summation order (an f32 destination is rounded per launch).
 // xs, ys: null for none; the destinations' scales ride along with the first source chunk, and not with set.
+// ww (f32 sources and destinations only; null for none): the destinations' f64 twins, written by the launch of
+// the last source chunk with the values it stores.
 int outer_chunks(ssp_ctx* ctx, const double* alphas, const void* const* xx, ssp_dtype tx, const double* xs, int k,
-                 void* const* yy, ssp_dtype ty, const double* ys, int m, size_t n, bool set) {
+                 void* const* yy, ssp_dtype ty, const double* ys, int m, size_t n, bool set, double* const* ww = nullptr) {
   // one wave per window of 2 x 64 quads, ctx->outer_per_cu workgroups per CU (SSP_OUTER_WG_PER_CU)
   const unsigned grid = ssp::stream_grid(ctx, n / 4 + 1, 2, unsigned(ctx->outer_per_cu));
   const auto staged = [&](const double* v, size_t count, const double** dev) {
@@ -622,6 +637,12 @@ int outer_chunks(ssp_ctx* ctx, const double* alphas, const void* const* xx, ssp_
       if (dev) SSP_TRY(staged(block.data(), block.size(), &a.alpha_dev));
       SSP_TRY(ssp::flush_uploads(ctx));
       const bool first = set && i0 == 0;  // the launch that writes the destinations without reading them
+      if (ww && i0 + ssp::kOuterSrc >= k) {  // the launch that stores the destinations' final values
+        for (int j = 0; j < mm; ++j) a.w[j] = ww[j0 + j];
+        first ? launch_outer_m<float, float, true, true>(ctx, grid, a) : launch_outer_m<float, float, false, true>(ctx, grid, a);
+        SSP_TRY_HIP(hipGetLastError());
+        continue;
+      }
       SSP_TRY(with_pair(tx, ty, [&](auto X, auto Y) {
         using TX = decltype(X);
         using TY = decltype(Y);
@@ -776,6 +797,58 @@ int ssp_q32_gemm_inner_cols(ssp_ctx* ctx, const double* const* xx, const double*
   }
   SSP_TRY(ssp::fold_finish(ctx, tail, res.data()));
   return deliver();
+}
+
+int ssp_q32_combine_widen(ssp_ctx* ctx, const double* alphas, const float* const* xx, int k, float* const* yy,
+                          double* const* ww, int m, size_t n) {
+  SSP_CHECK_CTX_KEEP_FILLS(ctx);
+  if (m < 0 || k < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_q32_combine_widen: negative dimension");
+  SSP_TRY(check_ptrs(reinterpret_cast<const void* const*>(xx), k, n, "ssp_q32_combine_widen"));
+  SSP_TRY(check_ptrs(reinterpret_cast<const void* const*>(yy), m, n, "ssp_q32_combine_widen"));
+  SSP_TRY(check_ptrs(reinterpret_cast<const void* const*>(ww), m, n, "ssp_q32_combine_widen"));
+  if (m == 0 || n == 0) return SSP_OK;
+  if (k > 0 && !alphas) return ssp::set_error(SSP_ERR_ARG, "ssp_q32_combine_widen: null alphas");
+  for (int j = 0; j < m; ++j) {
+    for (int i = 0; i < k; ++i)
+      if (static_cast<const void*>(yy[j]) == xx[i] || static_cast<const void*>(ww[j]) == xx[i])
+        return ssp::set_error(SSP_ERR_ARG, "ssp_q32_combine_widen: a destination aliases a source");
+    for (int l = 0; l < m; ++l)
+      if (static_cast<const void*>(ww[j]) == yy[l] || (l != j && (yy[l] == yy[j] || ww[l] == ww[j])))
+        return ssp::set_error(SSP_ERR_ARG, "ssp_q32_combine_widen: two destinations are the same vector");
+  }
+  // pending zero fills: the sources are read; the destinations are written in full and read by nothing, so
+  // theirs are dropped (one that only shares bytes with an f32 destination's odd end is stored first)
+  if (!ctx->pending_fills.empty()) {
+    for (int i = 0; i < k; ++i) SSP_TRY(ssp::flush_fills_over(ctx, xx[i], (n + 1) / 2));
+    for (int j = 0; j < m; ++j) {
+      SSP_TRY(ssp::overwrite_fills(ctx, yy[j], n / 2));
+      SSP_TRY(ssp::flush_fills_over(ctx, yy[j], (n + 1) / 2));
+      SSP_TRY(ssp::overwrite_fills(ctx, ww[j], n));
+    }
+  }
+  if (k == 0) {  // the sum of no sources
+    for (int j = 0; j < m; ++j) {
+      SSP_TRY(ssp_fill_f32(ctx, 0.0, yy[j], n));
+      SSP_TRY(convert(ctx, ww[j], SSP_F64, yy[j], SSP_F32, 1.0, n));
+    }
+    return SSP_OK;
+  }
+  if (ssp::exact_mode(ctx, n)) {  // ssp_mx_gemm_outer's exact path, then the widening copy
+    Scratch s(ctx);
+    std::vector<const double*> xw(static_cast<size_t>(k));
+    std::vector<double*> yw(static_cast<size_t>(m));
+    for (int i = 0; i < k; ++i) SSP_TRY(s.widen(xx[i], SSP_F32, n, &xw[size_t(i)]));
+    for (int j = 0; j < m; ++j) SSP_TRY(s.fresh(n, &yw[size_t(j)]));
+    SSP_TRY(ssp_gemm_outer_set_scaled(ctx, alphas, xw.data(), nullptr, k, yw.data(), m, n));
+    for (int j = 0; j < m; ++j) {
+      SSP_TRY(convert(ctx, yy[j], SSP_F32, yw[size_t(j)], SSP_F64, 1.0, n));
+      SSP_TRY(convert(ctx, ww[j], SSP_F64, yy[j], SSP_F32, 1.0, n));
+    }
+    return SSP_OK;
+  }
+  ssp::LedgerScope ls(ctx, "combine_widen_f32", (4.0 * k + 12.0 * m) * n);
+  return outer_chunks(ctx, alphas, reinterpret_cast<const void* const*>(xx), SSP_F32, nullptr, k,
+                      reinterpret_cast<void* const*>(yy), SSP_F32, nullptr, m, n, true, ww);
 }
 
 int ssp_alloc_f32(ssp_ctx* ctx, size_t n, float** out) {

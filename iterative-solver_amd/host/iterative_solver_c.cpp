@@ -72,6 +72,7 @@ struct Instance {
   void* refine_user = nullptr;
   double *scratch_p = nullptr, *scratch_a = nullptr;
   size_t scratch_ld = 0;
+  size_t scratch_rows = 0;
   bool scratch_device = false;
 };
 // The instance stack (reference IterativeSolverCMPI.cpp: std::stack<Instance>); the back is the top,
@@ -249,13 +250,16 @@ it::VecRef<Vec> first(std::vector<Vec>& v, size_t n) { return it::wrap(v.begin()
 
 // ---- refined mode (Q_REFINE; include/iterative_solver_c.h) ------------------------------------------------
 // The arrays of the running AddVector / AddVectorDevice / AddP call are the scratch of a refinement inside it:
-// the call exports every row at its end, so what the refinement leaves in them is overwritten.
+// the call exports every row at its end, so what the refinement leaves in them is overwritten.  So are the two
+// arrays of an EndIteration / EndIterationDevice call once they are imported: the scratch of a D-space rebuild
+// (Q_REFINE_DSPACE) inside it.  rows: how many rows the arrays hold.
 struct RefineScratch {
   Instance& in;
-  RefineScratch(Instance& i, double* p, double* a, size_t ld, bool device) : in(i) {
+  RefineScratch(Instance& i, double* p, double* a, size_t ld, bool device, size_t rows) : in(i) {
     in.scratch_p = p;
     in.scratch_a = a;
     in.scratch_ld = ld;
+    in.scratch_rows = rows;
     in.scratch_device = device;
   }
   ~RefineScratch() { in.scratch_p = in.scratch_a = nullptr; }
@@ -268,6 +272,9 @@ void refine_action(Instance& in, const it::CVecRef<Vec>& x, const it::VecRef<Vec
   const size_t m = x.size();
   if (!in.refine_fn || !in.scratch_p || !in.scratch_a)
     throw std::logic_error("refine: no IterativeSolverHbmSetRefineAction callback for this call");
+  if (m > in.scratch_rows)
+    throw std::logic_error("refine: the call's arrays hold " + std::to_string(in.scratch_rows) + " rows, the action needs " +
+                           std::to_string(m));
   double* const p = in.scratch_p;
   double* const g = in.scratch_a;
   const size_t ld = in.scratch_ld;
@@ -305,10 +312,12 @@ void store_diagonals_as_q(Instance& in) {
   if (in.solver->q_bytes() < sizeof(double) && in.diagonals) in.solver->quantise(it::wrap_arg(*in.diagonals));
 }
 
-// Q_STORAGE, Q_REFINE, Q_REFINE_KAPPA of an options string (keys upper-cased by parse_options).
+// Q_STORAGE, Q_REFINE, Q_REFINE_KAPPA, Q_REFINE_DSPACE, Q_REFINE_DSPACE_SLACK of an options string (keys
+// upper-cased by parse_options).
 struct QOptions {
-  bool f32 = false, refine = false, named = false;
+  bool f32 = false, refine = false, named = false, dspace = false;
   double kappa = 8.0;
+  int dspace_slack = -1;  // the solver's rule
 };
 QOptions q_options(const char* options) {
   QOptions q;
@@ -328,6 +337,15 @@ QOptions q_options(const char* options) {
     if (!q.refine) throw std::invalid_argument("Q_REFINE_KAPPA: needs Q_REFINE=1");
     q.kappa = std::stod(f->second);
     if (!(q.kappa > 0)) throw std::invalid_argument("Q_REFINE_KAPPA=" + f->second + ": must be positive");
+  }
+  if (auto f = m.find("Q_REFINE_DSPACE"); f != m.end()) {
+    q.dspace = facet.tobool(f->second);
+    if (q.dspace && !q.refine) throw std::invalid_argument("Q_REFINE_DSPACE: needs Q_REFINE=1");
+  }
+  if (auto f = m.find("Q_REFINE_DSPACE_SLACK"); f != m.end()) {
+    if (!q.dspace) throw std::invalid_argument("Q_REFINE_DSPACE_SLACK: needs Q_REFINE_DSPACE=1");
+    q.dspace_slack = std::stoi(f->second);
+    if (q.dspace_slack < 0) throw std::invalid_argument("Q_REFINE_DSPACE_SLACK=" + f->second + ": must not be negative");
   }
   return q;
 }
@@ -416,7 +434,7 @@ void IterativeSolverLinearEigensystemInitialize(size_t nQ, size_t nroot, size_t*
     const std::string method = algorithm ? algorithm : "";
     const auto q = q_options(options);
     if (q.named) {  // extension: the Q space in f32 and / or refined residuals, one-rank Davidson only
-      const char* which = q.f32 ? "Q_STORAGE=f32" : "Q_REFINE";
+      const char* which = q.f32 ? "Q_STORAGE=f32" : q.dspace ? "Q_REFINE_DSPACE" : "Q_REFINE";
       if (!(method == "Davidson" || method.empty()))
         throw std::invalid_argument(std::string(which) + ": available for the LinearEigensystem Davidson only, not " + method);
       if (in.dev->nranks() > 1)
@@ -438,8 +456,8 @@ void IterativeSolverLinearEigensystemInitialize(size_t nQ, size_t nroot, size_t*
     in.solver->set_convergence_threshold(thresh);
     in.solver->set_convergence_threshold_value(thresh_value);
     // the refined mode's scope is checked here, not in the middle of a solve: hermitian = 0, MAX_SIZE_QSPACE,
-    // RESET_D and RESET_D_MAX_Q_SIZE are errors naming the option
-    if (q.refine) in.solver->set_refine(true, q.kappa);
+    // RESET_D and RESET_D_MAX_Q_SIZE are errors naming the option (Q_REFINE_DSPACE=1 admits MAX_SIZE_QSPACE)
+    if (q.refine) in.solver->set_refine(true, q.kappa, q.dspace, q.dspace_slack);
     in.has_eigenvalues = true;
     setup(in, nQ, range_begin, range_end);
     push(std::move(in));
@@ -541,7 +559,7 @@ size_t IterativeSolverAddVector(size_t buffer_size, double* parameters, double* 
     ensure_r(in, buffer_size);
     upload(in, in.rp, buffer_size, parameters);
     upload(in, in.ra, buffer_size, action);
-    const RefineScratch scratch(in, parameters, action, in.dimension, false);
+    const RefineScratch scratch(in, parameters, action, in.dimension, false, buffer_size);
     const size_t nwork = add_vector_staged(in, buffer_size);
     // The reference's R vectors are views of these host arrays, so every vector the solver wrote
     // (solutions and residuals of all roots, batch by batch) reaches the caller; sync gathers the
@@ -597,6 +615,7 @@ size_t IterativeSolverEndIteration(size_t buffer_size, double* solution, double*
     ensure_r(in, buffer_size);
     upload(in, in.rp, buffer_size, solution);
     upload(in, in.ra, buffer_size, residual);
+    const RefineScratch scratch(in, solution, residual, in.dimension, false, buffer_size);  // a D-space rebuild's
     const size_t result = in.solver->end_iteration(first(in.rp, buffer_size), first(in.ra, buffer_size));
     if (rounds_new_parameters(in)) in.solver->quantise(first(in.rp, std::min(result, buffer_size)));
     download(in, in.rp, buffer_size, solution);
@@ -651,7 +670,7 @@ size_t IterativeSolverAddP(size_t buffer_size, size_t nP, const size_t* offsets,
         check(ssp_upload(I.dev->ctx(), act[k].get().data_wo(), host.data() + k * I.dimension + I.offset, I.local),
               "ssp_upload");
     };
-    const RefineScratch scratch(in, parameters, action, in.dimension, false);
+    const RefineScratch scratch(in, parameters, action, in.dimension, false, buffer_size);
     const size_t nwork =
         in.solver->add_p(it::cwrap(pvectors), ppm, first(in.rp, buffer_size), first(in.ra, buffer_size), apply);
     download(in, in.rp, buffer_size, parameters);
@@ -673,7 +692,7 @@ size_t IterativeSolverHbmAddVectorDevice(size_t buffer_size, double* parameters,
     ensure_r(in, buffer_size);
     import_rows(in, in.rp, buffer_size, parameters, ld);
     import_rows(in, in.ra, buffer_size, action, ld);
-    const RefineScratch scratch(in, parameters, action, ld, true);
+    const RefineScratch scratch(in, parameters, action, ld, true, buffer_size);
     const size_t nwork = add_vector_staged(in, buffer_size);
     export_rows(in, in.rp, buffer_size, parameters, ld);
     export_rows(in, in.ra, buffer_size, action, ld);
@@ -715,6 +734,7 @@ size_t IterativeSolverHbmEndIterationDevice(size_t buffer_size, double* solution
     ensure_r(in, buffer_size);
     import_rows(in, in.rp, buffer_size, solution, ld);
     import_rows(in, in.ra, buffer_size, residual, ld);
+    const RefineScratch scratch(in, solution, residual, ld, true, buffer_size);  // a D-space rebuild's
     const size_t result = in.solver->end_iteration(first(in.rp, buffer_size), first(in.ra, buffer_size));
     // refined mode over an f32 Q space: the new parameter rows leave rounded, by the export itself where the
     // library has the export that rounds, else by a pass over the staging vectors first (the same bits)
@@ -890,6 +910,14 @@ int IterativeSolverHbmRefineStatistics(int* refined_actions, int* first_refined_
   if (refined_actions) *refined_actions = s.refined_actions();
   if (first_refined_iteration) *first_refined_iteration = s.first_refined_iteration();
   if (max_delta) *max_delta = s.max_refine_delta();
+  return 0;
+}
+
+int IterativeSolverHbmRefineDspaceStats(int* rebuilds, int* actions) {
+  if (instances.empty()) return 1;
+  const auto& s = *instances.back()->solver;
+  if (rebuilds) *rebuilds = s.dspace_rebuilds();
+  if (actions) *actions = s.dspace_actions();
   return 0;
 }
 

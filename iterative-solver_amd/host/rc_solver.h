@@ -50,12 +50,17 @@ class RcSolver {
   virtual bool eigenvalues(std::vector<double>& out) const = 0;
   virtual bool working_set_eigenvalues(std::vector<double>& out) const = 0;
   // refined mode (itsolv_hbm/solvers.h set_refine)
-  virtual void set_refine(bool on, double kappa) = 0;  //!< also checks the mode's scope (errors name the option)
+  //! also checks the mode's scope (errors name the option); dspace: with the consistent D space (set_refine_dspace),
+  //! dspace_slack >= 0: DavidsonSolver::set_refine_dspace_slack (negative: the solver's rule)
+  virtual void set_refine(bool on, double kappa, bool dspace = false, int dspace_slack = -1) = 0;
   virtual bool refine() const = 0;
   virtual void set_refine_action(action_hook_type hook) = 0;
   virtual int refined_actions() const = 0;
   virtual int first_refined_iteration() const = 0;
   virtual double max_refine_delta() const = 0;
+  virtual bool refine_dspace() const = 0;
+  virtual int dspace_rebuilds() const = 0;
+  virtual int dspace_actions() const = 0;
   //! bytes per stored Q element
   virtual size_t q_bytes() const = 0;
   //! rounds the vectors to the Q storage format in place (nothing for a Q space stored as R)
@@ -108,10 +113,18 @@ class RcSolverOf final : public RcSolver {
     out = m_s->working_set_eigenvalues();
     return true;
   }
-  void set_refine(bool on, double kappa) override {
-    if (on) m_s->validate_refine();
+  void set_refine(bool on, double kappa, bool dspace = false, int dspace_slack = -1) override {
+    if (on && !dspace) m_s->validate_refine();
     m_s->set_refine(on, kappa);
+    if (on && dspace) {  // the scope depends on the option: checked with it set
+      m_s->set_refine_dspace(true);
+      m_s->validate_refine();
+      if (auto* d = dynamic_cast<it::DavidsonSolver<Vec, Q, SparseP>*>(m_s.get())) d->set_refine_dspace_slack(dspace_slack);
+    }
   }
+  bool refine_dspace() const override { return m_s->refine_dspace(); }
+  int dspace_rebuilds() const override { return m_s->dspace_rebuilds(); }
+  int dspace_actions() const override { return m_s->dspace_actions(); }
   bool refine() const override { return m_s->refine(); }
   void set_refine_action(action_hook_type hook) override { m_s->set_refine_action(std::move(hook)); }
   int refined_actions() const override { return m_s->refined_actions(); }

@@ -1,7 +1,8 @@
 // Davidson with the Q space stored in f32 (include/itsolv_hbm.h *_q32): the restated solver over
 // R = hbm::Vec (f64), Q = hbm::VecF32, on the handlers of itsolv_hbm/hbm_handlers_f32.h.  The problems,
 // the runner and the result layout are those of host/itsolv_capi.cpp.  The *_q32_refined entries run the
-// same solver in its refined mode (itsolv_hbm/solvers.h set_refine).
+// same solver in its refined mode (itsolv_hbm/solvers.h set_refine), the *_q32_refined_dspace entries with
+// the consistent D space on top (set_refine_dspace), which admits max_size_qspace.
 //
 // This file lives outside host/ on purpose: every host/*.cpp is also built against the CPU emulation of
 // the f64 C ABI, which has no mixed-precision entry points.
@@ -17,7 +18,7 @@ thread_local pr::RefineStats g_refine_stats;  // itsolv_q32_refine_stats()
 
 // refine: null for the plain f32 Q space; else the refined mode (kappa <= 0: the default).
 int synth_q32(ssp_ctx* ctx, size_t n, const sspx_synth* spec, const itsolv_options* opt, const double* kappa,
-              itsolv_result* out, double* solutions_out) {
+              itsolv_result* out, double* solutions_out, bool dspace = false) {
   return guarded([&] {
     auto dev = borrow(ctx);
     const auto o = opts_or_default(opt);
@@ -31,12 +32,12 @@ int synth_q32(ssp_ctx* ctx, size_t n, const sspx_synth* spec, const itsolv_optio
           auto v = x.local_values();
           std::memcpy(solutions_out + r * v.size(), v.data(), v.size() * sizeof(double));
         },
-        residual_norms_batch(problem, dev, n), kappa, kappa ? &g_refine_stats : nullptr);
+        residual_norms_batch(problem, dev, n), kappa, kappa ? &g_refine_stats : nullptr, dspace);
   });
 }
 
 int dense_q32(ssp_ctx* ctx, const double* h, size_t n, const itsolv_options* opt, const double* kappa,
-              itsolv_result* out, double* solutions_out) {
+              itsolv_result* out, double* solutions_out, bool dspace = false) {
   return guarded([&] {
     auto dev = borrow(ctx);
     const auto o = opts_or_default(opt);
@@ -50,7 +51,7 @@ int dense_q32(ssp_ctx* ctx, const double* h, size_t n, const itsolv_options* opt
           auto v = x.local_values();
           std::memcpy(solutions_out + r * n, v.data(), n * sizeof(double));
         },
-        {}, kappa, kappa ? &g_refine_stats : nullptr);
+        {}, kappa, kappa ? &g_refine_stats : nullptr, dspace);
   });
 }
 
@@ -82,6 +83,28 @@ int itsolv_davidson_dense_q32_refined(ssp_ctx* ctx, const double* h, size_t n, c
   g_refine_stats = pr::RefineStats{};
   const double kappa = kappa_of(refine);
   return dense_q32(ctx, h, n, opt, &kappa, out, solutions_out);
+}
+
+int itsolv_davidson_synth_q32_refined_dspace(ssp_ctx* ctx, size_t n, const sspx_synth* spec, const itsolv_options* opt,
+                                             const itsolv_q32_refine* refine, itsolv_result* out,
+                                             double* solutions_out) {
+  g_refine_stats = pr::RefineStats{};
+  const double kappa = kappa_of(refine);
+  return synth_q32(ctx, n, spec, opt, &kappa, out, solutions_out, true);
+}
+
+int itsolv_davidson_dense_q32_refined_dspace(ssp_ctx* ctx, const double* h, size_t n, const itsolv_options* opt,
+                                             const itsolv_q32_refine* refine, itsolv_result* out,
+                                             double* solutions_out) {
+  g_refine_stats = pr::RefineStats{};
+  const double kappa = kappa_of(refine);
+  return dense_q32(ctx, h, n, opt, &kappa, out, solutions_out, true);
+}
+
+int itsolv_q32_dspace_stats(int* rebuilds, int* actions) {
+  if (rebuilds) *rebuilds = g_refine_stats.dspace_rebuilds;
+  if (actions) *actions = g_refine_stats.dspace_actions;
+  return 0;
 }
 
 int itsolv_q32_refine_stats(int* refined_actions, int* first_refined_iteration, double* max_delta) {

@@ -376,6 +376,16 @@ bool fused_new_combinations(H&, const Matrix<double>&, const std::vector<const Q
   return false;
 }
 
+// The same hook for the refined mode's consistent D space (rspace.h construct_dspace_refined), where Q is
+// stored narrower than R: out_q as above, and out_r[i] = the stored (rounded) out_q[i] widened to R's format,
+// both written by the one pass; returns false, touching nothing, when the handler has no such form (the caller
+// then builds out_q as above and copies each into out_r).  Found by argument-dependent lookup.
+template <class H, class Q, class RefR>
+bool fused_new_combinations_widened(H&, const Matrix<double>&, const std::vector<const Q*>&, std::vector<Q>&,
+                                    const RefR&) {
+  return false;
+}
+
 // Hook for the new rows of the subspace matrices (xspace::update_qspace_data, reference
 // XSpace.h:30-83, which issues one overlap per block): out = the overlaps of `rows` with the column
 // sets `cols` concatenated, in one batched gemm_inner that reads the rows once per launch instead of

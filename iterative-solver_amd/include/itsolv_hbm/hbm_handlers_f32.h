@@ -453,4 +453,39 @@ inline bool fused_new_combinations(array::ArrayHandler<VecF32, VecF32>&, const i
   return true;
 }
 
+// The same with the new vectors' f64 twins (array::fused_new_combinations_widened hook, the consistent D space
+// of rspace.h construct_dspace_refined): one ssp_q32_combine_widen writes each new f32 vector and, into twin[j],
+// the value it stored, widened -- the pass reads the sources once and neither destination set.  From
+// fused_min_size(), as the other fused solver passes (below it: fused_new_combinations, then the widening copies).
+inline bool fused_new_combinations_widened(array::ArrayHandler<VecF32, VecF32>&,
+                                           const itsolv::subspace::Matrix<double>& coeff,
+                                           const std::vector<const VecF32*>& src, std::vector<VecF32>& out,
+                                           const itsolv::VecRef<Vec>& twin) {
+  const size_t nout = coeff.rows(), k = src.size();
+  if (k == 0 || coeff.cols() != k || twin.size() < nout || src.front()->size() < fused_min_size()) return false;
+  const VecF32& v0 = *src.front();
+  std::vector<const float*> xp;
+  for (auto* v : src) xp.push_back(v->data());
+  std::vector<double> alphas(k * nout);  // alphas[i * m + j]: source i, destination j
+  for (size_t j = 0; j < nout; ++j)
+    for (size_t i = 0; i < k; ++i) alphas[i * nout + j] = coeff(j, i);
+  for (size_t j = 0; j < nout; ++j) {
+    const Vec& w = twin[j].get();
+    if (w.size() != v0.size() || w.offset() != v0.offset() || w.local_size() != v0.local_size())
+      throw array::util::ArrayHandlerError{"fused_new_combinations_widened: arrays have different distributions"};
+  }
+  const size_t first = out.size();
+  for (size_t j = 0; j < nout; ++j) out.push_back(v0.alloc_like());
+  std::vector<float*> yp;
+  std::vector<double*> wp;
+  for (size_t j = 0; j < nout; ++j) {
+    yp.push_back(out[first + j].data());
+    wp.push_back(twin[j].get().data_wo());
+  }
+  check(ssp_q32_combine_widen(v0.ctx(), alphas.data(), xp.data(), int(k), yp.data(), wp.data(), int(nout),
+                              v0.local_size()),
+        "ssp_q32_combine_widen");
+  return true;
+}
+
 }  // namespace molpro::linalg::hbm

@@ -165,18 +165,23 @@ struct RefineStats {
   int refined_actions = 0;
   int first_refined_iteration = 0;
   double max_delta = 0;
+  // with the consistent D space (solvers.h set_refine_dspace): its rebuilds and the actions spent on them
+  int dspace_rebuilds = 0;
+  int dspace_actions = 0;
 };
 
 // refine_kappa: null for the plain solve; else the refined mode with that kappa (<= 0: the default), and
-// refine_stats (optional) filled after the solve.
+// refine_stats (optional) filled after the solve.  refine_dspace: the refined mode's consistent D space
+// (set_refine_dspace), which admits max_size_qspace.
 template <class R, class Q, class P>
 void run_davidson(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Problem<R, P>& problem,
                   const std::function<R()>& make_vec, const std::function<double(const R&, double)>& residual_norm,
                   const itsolv_options& o, itsolv_result& out, const std::function<void(size_t, const R&)>& emit,
                   const ResidualNormsBatch<R>& residual_norms_batch = {}, const double* refine_kappa = nullptr,
-                  RefineStats* refine_stats = nullptr) {
+                  RefineStats* refine_stats = nullptr, bool refine_dspace = false) {
   LinearEigensystemDavidson<R, Q, P> solver(handlers);
   if (refine_kappa) solver.set_refine(true, *refine_kappa);
+  if (refine_dspace) solver.set_refine_dspace(true);
   LinearEigensystemDavidsonOptions opt;
   apply_options(o, opt);
   if (o.max_size_qspace > 0) opt.max_size_qspace = o.max_size_qspace;
@@ -205,6 +210,8 @@ void run_davidson(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Proble
     refine_stats->first_refined_iteration = solver.first_refined_iteration();
     refine_stats->max_delta = 0;
     for (double d : solver.refine_delta()) refine_stats->max_delta = std::max(refine_stats->max_delta, d);
+    refine_stats->dspace_rebuilds = solver.dspace_rebuilds();
+    refine_stats->dspace_actions = solver.dspace_actions();
   }
   const auto& st = solver.statistics();
   out.iterations = st.iterations;

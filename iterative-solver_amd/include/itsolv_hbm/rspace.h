@@ -132,6 +132,20 @@ inline Matrix<double> remove_null_projected_solutions(const Matrix<double>& proj
   return out;
 }
 
+// The new D space in terms of [Q_delete | D]: the solutions' projections, stabilised and normalised in the
+// metric S (reference propose_rspace.h:349-375); row i holds the coefficients of new D vector i.
+inline Matrix<double> new_dspace_coefficients(const Matrix<double>& sol, const Dimensions& d, const Matrix<double>& S,
+                                              const std::vector<int>& qdel, double norm_thresh, double svd_thresh,
+                                              Logger& log) {
+  auto proj = construct_projected_solution(sol, d, qdel);
+  auto ovp = construct_projected_solutions_overlap(proj, S, d, qdel);
+  remove_null_norm_and_normalise(proj, ovp, norm_thresh, log);
+  proj = remove_null_projected_solutions(proj, ovp, svd_thresh);
+  ovp = construct_projected_solutions_overlap(proj, S, d, qdel);
+  remove_null_norm_and_normalise(proj, ovp, norm_thresh, log);
+  return proj;
+}
+
 }  // namespace dspace
 
 // Overlap of P+Q+D plus new parameters appended last (reference :271-300).
@@ -255,13 +269,7 @@ std::tuple<std::vector<Q>, std::vector<Q>> construct_dspace(const Matrix<double>
                                                             double svd_thresh, array::ArrayHandler<Q, Q>& h,
                                                             Logger& log) {
   const auto d = xs.dimensions();
-  const auto& S = xs.data.at(EqnData::S);
-  auto proj = dspace::construct_projected_solution(sol, d, qdel);
-  auto ovp = dspace::construct_projected_solutions_overlap(proj, S, d, qdel);
-  dspace::remove_null_norm_and_normalise(proj, ovp, norm_thresh, log);
-  proj = dspace::remove_null_projected_solutions(proj, ovp, svd_thresh);
-  ovp = dspace::construct_projected_solutions_overlap(proj, S, d, qdel);
-  dspace::remove_null_norm_and_normalise(proj, ovp, norm_thresh, log);
+  const auto proj = dspace::new_dspace_coefficients(sol, d, xs.data.at(EqnData::S), qdel, norm_thresh, svd_thresh, log);
   const size_t nD = proj.rows(), nqd = qdel.size();
   const auto qp = xs.cparamsq(), qa = xs.cactionsq(), dp = xs.cparamsd(), da = xs.cactionsd();
   std::vector<Q> newp, newa;
@@ -312,6 +320,60 @@ std::tuple<std::vector<Q>, std::vector<Q>> construct_dspace(const Matrix<double>
     h.scal(1. / nrm, newa[i]);
   }
   return {std::move(newp), std::move(newa)};
+}
+
+// An R vector shaped like x whose contents are about to be overwritten: without a copy where the container
+// can be allocated uninitialised (alloc_like), else a copy.
+template <class R, class = void>
+struct has_alloc_like : std::false_type {};
+template <class R>
+struct has_alloc_like<R, std::void_t<decltype(std::declval<const R&>().alloc_like())>> : std::true_type {};
+template <class R>
+R scratch_like(array::ArrayHandler<R, R>& h, const R& x) {
+  if constexpr (has_alloc_like<R>::value) return x.alloc_like();
+  else return h.copy(x);
+}
+
+// The parameters of the new D space in the refined mode (solvers.h set_refine_dspace), for a Q space stored
+// narrower than R: the coefficients of construct_dspace, then one pass over the source PARAMETERS (the Q vectors
+// being deleted, then the old D) that stores each new vector rounded once and, in twin[i], that stored value in
+// R's format -- the vector whose action the solver takes next, so that the D space's actions belong to its
+// stored parameters.  The stored actions are not read, and nothing is rescaled after the rounding (a scal of
+// a stored vector would round it again): the coefficients are normalised in the metric S and S(D, D), built
+// from the twins, carries the actual norms.  twin: at least as many R vectors as `sol` has rows.
+template <class R, class Q, class P>
+std::vector<Q> construct_dspace_refined(const Matrix<double>& sol, const subspace::XSpace<R, Q, P>& xs,
+                                        const std::vector<int>& qdel, double norm_thresh, double svd_thresh,
+                                        ArrayHandlers<R, Q, P>& h, const VecRef<R>& twin, Logger& log) {
+  const auto d = xs.dimensions();
+  const auto proj = dspace::new_dspace_coefficients(sol, d, xs.data.at(EqnData::S), qdel, norm_thresh, svd_thresh, log);
+  const size_t nD = proj.rows(), nqd = qdel.size();
+  if (twin.size() < nD) throw std::logic_error("construct_dspace_refined: too few twin vectors");
+  const auto qp = xs.cparamsq(), dp = xs.cparamsd();
+  std::vector<const Q*> src;
+  for (size_t j = 0; j < nqd; ++j) src.push_back(&qp.at(qdel[j]).get());
+  for (size_t j = 0; j < d.nD; ++j) src.push_back(&dp.at(j).get());
+  std::vector<Q> newp;
+  if (nD == 0 || src.empty()) return newp;
+  Matrix<double> c(std::make_pair(nD, src.size()));
+  for (size_t i = 0; i < nD; ++i)
+    for (size_t j = 0; j < src.size(); ++j) c(i, j) = proj(i, j);
+  auto& hqq = h.qq();
+  using array::fused_new_combinations;
+  using array::fused_new_combinations_widened;
+  if (fused_new_combinations_widened(hqq, c, src, newp, VecRef<R>(twin.begin(), twin.begin() + long(nD)))) return newp;
+  if (!fused_new_combinations(hqq, c, src, newp)) {
+    for (size_t i = 0; i < nD; ++i) {
+      newp.emplace_back(hqq.copy(*src.front()));
+      hqq.fill(0, newp.back());
+    }
+    auto lp = hqq.lazy_handle();
+    for (size_t i = 0; i < nD; ++i)
+      for (size_t j = 0; j < src.size(); ++j) lp.axpy(c(i, j), *src[j], newp.at(i));
+    lp.eval();
+  }
+  for (size_t i = 0; i < nD; ++i) h.rq().copy(twin[i], newp[i]);
+  return newp;
 }
 
 // Sequential self-orthonormalisation of R; indices whose norm is below norm_thresh are returned

@@ -454,8 +454,30 @@ class IterativeSolverTemplate {
     m_refined_actions = 0;
     m_first_refined_iteration = 0;
     m_refine_delta.clear();
+    m_refine_dspace = false;
+    m_dspace_rebuilds = m_dspace_actions = 0;
   }
   bool refine() const { return m_refine; }
+  // The refined mode under a Q-space limit (opt-in; call after set_refine(true)).  With it, check_refine accepts
+  // a finite max_size_qspace, and whenever the limit deletes Q vectors the D space is rebuilt consistently:
+  // the new D parameters are written by one pass over the deleted Q and old D PARAMETERS, rounded once, with
+  // their values in R's format beside them (rspace.h construct_dspace_refined); the D actions are true actions
+  // of exactly those vectors, one call of the action hook for all of them; and the D blocks of S and H come
+  // from these in R's precision (subspace.h update_dspace_refined).  The bound delta_i then has the D terms
+  // u sum_d |c_di| |a_d|.  Cost: nD <= n_roots actions per rebuild, a rebuild in every iteration in which the
+  // limit deletes something -- which propose_rspace makes rarer by cutting the Q space below the limit
+  // (DavidsonSolver::set_refine_dspace_slack).  reset_D / reset_D_max_Q_size stay outside the scope.
+  void set_refine_dspace(bool on) {
+    if (on && !m_refine) throw std::logic_error("refine_dspace: needs the refined mode (set_refine) first");
+    m_xspace->set_refined_dspace(on);
+    m_refine_dspace = on;
+    m_dspace_rebuilds = m_dspace_actions = 0;
+  }
+  bool refine_dspace() const { return m_refine_dspace; }
+  //! rebuilds of the D space under the Q-space limit (in either mode), and the actions the refined mode spent
+  //! on them (not in refined_actions())
+  int dspace_rebuilds() const { return m_dspace_rebuilds; }
+  int dspace_actions() const { return m_dspace_actions; }
   double refine_kappa() const { return m_refine_kappa; }
   //! actions spent on refined residuals; the iteration (from 1) of the first; the last delta of each root
   int refined_actions() const { return m_refined_actions; }
@@ -649,14 +671,12 @@ class IterativeSolverTemplate {
   void refine_residuals(const std::vector<int>& roots, const VecRef<R>& parameters, const VecRef<R>& action,
                         std::vector<double>& errors) {
     const auto& d = m_xspace->dimensions();
-    if (d.nQ == 0) return;  // nothing is stored rounded yet
-    if (d.nD != 0) throw std::runtime_error("refine: a D space is not supported");
-    if (!m_action_hook)
-      throw std::logic_error(
-          "refine: needs the problem's action, which only solve() provides (not add_vector by hand) unless "
-          "set_refine_action has given it (C API: IterativeSolverHbmSetRefineAction)");
+    if (d.nQ + (m_refine_dspace ? d.nD : 0) == 0) return;  // nothing is stored rounded yet
+    if (d.nD != 0 && !m_refine_dspace) throw std::runtime_error("refine: a D space is not supported");
+    require_action_hook();
     check_refine();
     const auto& norms = m_xspace->q_action_norms();
+    const auto& dnorms = m_xspace->d_action_norms();
     const auto& sol = m_subspace_solver->solutions();
     constexpr double u = 5.9604644775390625e-08;  // 2^-24, the unit roundoff of binary32
     if (m_refine_delta.size() < sol.rows()) m_refine_delta.resize(sol.rows(), 0.0);
@@ -666,6 +686,7 @@ class IterativeSolverTemplate {
     for (size_t i = 0; i < roots.size(); ++i) {
       double delta = 0;
       for (size_t j = 0; j < d.nQ; ++j) delta += std::abs(sol(size_t(roots[i]), d.oQ + j)) * norms.at(j);
+      for (size_t j = 0; j < d.nD; ++j) delta += std::abs(sol(size_t(roots[i]), d.oD + j)) * dnorms.at(j);
       delta *= u;
       m_refine_delta[size_t(roots[i])] = delta;
       if (errors[i] <= std::max(m_refine_kappa * delta, m_convergence_threshold + delta)) {
@@ -689,6 +710,13 @@ class IterativeSolverTemplate {
     }
     m_residual_norms2.clear();
     for (size_t i = 0; i < e.size(); ++i) errors[slot[i]] = e[i];
+  }
+
+  void require_action_hook() const {
+    if (!m_action_hook)
+      throw std::logic_error(
+          "refine: needs the problem's action, which only solve() provides (not add_vector by hand) unless "
+          "set_refine_action has given it (C API: IterativeSolverHbmSetRefineAction)");
   }
 
   void check_roots(const std::vector<int>& roots, size_t nparams) const {
@@ -722,6 +750,9 @@ class IterativeSolverTemplate {
   int m_refined_actions = 0;
   int m_first_refined_iteration = 0;  // 0: none yet
   std::vector<double> m_refine_delta;
+  bool m_refine_dspace = false;  // set_refine_dspace
+  int m_dspace_rebuilds = 0;
+  int m_dspace_actions = 0;
 };
 
 // ---- Davidson ----------------------------------------------------------------------------------
@@ -765,6 +796,26 @@ class DavidsonSolver : public IterativeSolverTemplate<R, Q, P> {
   void set_max_size_qspace(int n) {
     m_max_size_qspace = n;
     if (m_resetter.get_max_Qsize() > m_max_size_qspace) m_resetter.set_max_Qsize(size_t(m_max_size_qspace));
+  }
+  //! How far below max_size_qspace a rebuild of the refined mode's D space (set_refine_dspace) cuts the Q space.
+  //! 0 is the reference's schedule: delete just enough, so a rebuild in every iteration once the Q space is
+  //! full.  Unset (the default, or a negative n) it is a rule in whole working sets (less than one spaces
+  //! nothing): two per rebuild -- a rebuild every third iteration -- or one, whichever stays under a quarter of
+  //! the limit; none where the limit is that tight, because there the smaller Q space costs more iterations
+  //! than the rarer rounding saves.  The rule's constants were measured on one dense fixture
+  //! (profiles/r14/q32_refined_dspace.md); a caller who knows better sets the value.  A value is cut to leave
+  //! at least n_roots Q vectors.
+  void set_refine_dspace_slack(int n) {
+    if (n < 0)
+      m_refine_dspace_slack.reset();
+    else
+      m_refine_dspace_slack = n;
+  }
+  int refine_dspace_slack() const {
+    if (m_max_size_qspace == std::numeric_limits<int>::max()) return 0;
+    const size_t nr = this->n_roots(), quarter4 = size_t(m_max_size_qspace);  // 4 x a quarter of the limit
+    if (m_refine_dspace_slack) return std::min(*m_refine_dspace_slack, std::max(0, m_max_size_qspace - int(nr)));
+    return 4 * 2 * nr < quarter4 ? int(2 * nr) : 4 * nr < quarter4 ? int(nr) : 0;
   }
   void set_hermiticity(bool h) {
     m_hermiticity = h;
@@ -818,13 +869,30 @@ class DavidsonSolver : public IterativeSolverTemplate<R, Q, P> {
     auto& log = *this->m_logger;
     const auto solutions = ss.solutions();
     auto q_delete = detail::limit_qspace_size(xs.dimensions(), size_t(m_max_size_qspace), solutions, log);
-    if (!q_delete.empty()) {
+    // Refined mode with a D space: a rebuild costs nD actions AND rounds the D part of the solutions to f32
+    // once more, which takes 2^-24 of each of its elements out of the subspace; later iterations restore that
+    // only at the solver's convergence rate.  Deleting just enough in every iteration (the reference's schedule)
+    // rebuilds in every iteration, and the residual then settles at a few times that loss.  So when the Q space
+    // passes the limit it is cut back below it, by refine_dspace_slack() vectors: the limit holds as before, and
+    // a rebuild comes once in several iterations, each loss decayed before the next.
+    if (!q_delete.empty() && this->m_refine && this->m_refine_dspace && !this->working_set().empty() &&
+        refine_dspace_slack() > 0)
+      q_delete = detail::limit_qspace_size(xs.dimensions(), size_t(m_max_size_qspace - refine_dspace_slack()), solutions, log);
+    if (!q_delete.empty() && this->m_refine && this->m_refine_dspace) {
+      // An empty working set ends the solve: nothing more is added, and a rebuild would round the converged
+      // solutions once more after their (true) residuals were reported -- the subspace stays as it is.
+      if (!this->working_set().empty()) {
+        rebuild_dspace_refined(solutions, q_delete, parameters);
+        ss.solve(xs.data, solutions.rows());
+      }
+    } else if (!q_delete.empty()) {
       auto [dp, da] = detail::construct_dspace(solutions, xs, q_delete, norm_thresh, svd_thresh, h.qq(), log);
       std::sort(q_delete.begin(), q_delete.end(), std::greater<int>());
       for (int iq : q_delete) xs.eraseq(size_t(iq));
       auto wdp = wrap(dp);
       auto wda = wrap(da);
       xs.update_dspace(wdp, wda);
+      this->m_dspace_rebuilds++;
       ss.solve(xs.data, solutions.rows());
     }
     auto wres = wrap(residuals.begin(), residuals.begin() + this->working_set().size());
@@ -852,6 +920,36 @@ class DavidsonSolver : public IterativeSolverTemplate<R, Q, P> {
     return detail::get_new_working_set(this->working_set(), cwrap(residuals), cwrap(wres));
   }
 
+  // The D space rebuilt in the refined mode (set_refine_dspace).  `parameters` are free until the end of
+  // propose_rspace, which overwrites them (nothing reads them in between): they hold the new D parameters in
+  // R's format; the actions get R vectors of their own for the duration.
+  void rebuild_dspace_refined(const subspace::Matrix<double>& solutions, std::vector<int> q_delete, const VecRef<R>& parameters) {
+    auto& xs = *this->m_xspace;
+    auto& h = *this->m_handlers;
+    this->require_action_hook();
+    if (parameters.empty()) throw std::logic_error("refine_dspace: no parameter vectors to work in");
+    std::vector<R> spare;  // where the caller gave fewer vectors than there are solutions
+    spare.reserve(solutions.rows());
+    VecRef<R> twin(parameters.begin(), parameters.end());
+    while (twin.size() < solutions.rows()) {
+      spare.emplace_back(detail::scratch_like(h.rr(), parameters.front().get()));  // write-only: no copy
+      twin.emplace_back(spare.back());
+    }
+    auto dp = detail::construct_dspace_refined(solutions, xs, q_delete, norm_thresh, svd_thresh, h, twin, *this->m_logger);
+    const size_t nD = dp.size();
+    std::vector<R> act;
+    act.reserve(nD);
+    for (size_t i = 0; i < nD; ++i) act.emplace_back(detail::scratch_like(h.rr(), twin[i].get()));
+    const auto w = cwrap(twin.begin(), twin.begin() + long(nD));
+    if (nD > 0) this->m_action_hook(w, wrap(act));
+    this->m_dspace_rebuilds++;
+    this->m_dspace_actions += int(nD);
+    std::sort(q_delete.begin(), q_delete.end(), std::greater<int>());
+    for (int iq : q_delete) xs.eraseq(size_t(iq));
+    xs.update_dspace_refined(dp, w, cwrap(act));
+  }
+
+  std::optional<int> m_refine_dspace_slack;  // set_refine_dspace_slack; unset: the default rule
   int m_max_size_qspace = std::numeric_limits<int>::max();
   detail::DSpaceResetter<Q> m_resetter;
   bool m_hermiticity = false;
@@ -891,10 +989,14 @@ class LinearEigensystemDavidson : public DavidsonSolver<R, Q, P> {
   void check_refine() const override {
     constexpr int unlimited = std::numeric_limits<int>::max();
     if (!this->get_hermiticity()) throw std::runtime_error("refine: needs hermitian = 1 (hermiticity)");
-    if (this->get_max_size_qspace() != unlimited)
+    if (this->get_max_size_qspace() != unlimited && !this->m_refine_dspace)
       throw std::runtime_error("refine: max_size_qspace must be unlimited (a D space is not supported)");
     if (this->get_reset_D() != unlimited) throw std::runtime_error("refine: reset_D must be off (a D space is not supported)");
-    if (this->get_reset_D_maxQ_size() != unlimited)
+    // (set_max_size_qspace lowers reset_D_max_Q_size to the limit with it: that implied value is no request
+    // for a reset, which reset_D alone turns on.  A caller's own reset_D_max_Q_size equal to the limit cannot be
+    // told from it and passes too; it has no effect while reset_D is refused above.)
+    const bool implied = this->m_refine_dspace && this->get_reset_D_maxQ_size() == this->get_max_size_qspace();
+    if (this->get_reset_D_maxQ_size() != unlimited && !implied)
       throw std::runtime_error("refine: reset_D_max_Q_size must be unlimited (a D space is not supported)");
   }
 

@@ -248,16 +248,99 @@ class XSpace {
   void set_refined(bool on) {
     if (on && m_dim.nQ + m_dim.nD != 0) throw std::logic_error("refine: must be set on an empty subspace");
     m_refined = on;
+    m_refined_dspace = false;
     m_q_action_norms.clear();
+    m_d_action_norms.clear();
   }
   bool refined() const { return m_refined; }
   const std::vector<double>& q_action_norms() const { return m_q_action_norms; }
+  // The refined mode with a D space (solvers.h set_refine_dspace): the D space is then replaced by
+  // update_dspace_refined only, whose stored actions are true actions of the stored parameters, and the refined
+  // rows of new_qspace_data take the D columns from the stored D parameters as they do for Q.
+  void set_refined_dspace(bool on) {
+    if (on && !m_refined) throw std::logic_error("refine: a consistent D space needs the refined mode");
+    m_refined_dspace = on;
+  }
+  bool refined_dspace() const { return m_refined_dspace; }
+  const std::vector<double>& d_action_norms() const { return m_d_action_norms; }
+
+  // Replaces the D space in the refined mode.  params: the new stored D parameters; w[i]: params[i] in R's
+  // format, exactly; a[i] = H w[i] in R's precision.  The stored D actions are the narrowing copies of a, their
+  // norms |a_i| are kept beside the D space (d_action_norms, D order), and the D blocks of S and H come from
+  // w and a against the stored parameters: S(D,D) = w.w, S(D,Q) = w.q, S(D,P), H(D,D) = w.a, H(Q,D) = q.a,
+  // H(P,D) = p.a, H(D,Q) and H(D,P) their transposes (hermitian).  The stored Q actions are not read.
+  void update_dspace_refined(std::vector<Q>& params, const CVecRef<R>& w, const CVecRef<R>& a) {
+    if (!m_refined || !m_refined_dspace) throw std::logic_error("refine: update_dspace_refined needs set_refined_dspace");
+    if (!m_hermitian || m_action_dot_action) throw std::logic_error("refine: hermitian kernels only");
+    const size_t nd = params.size();
+    if (w.size() != nd || a.size() != nd) throw std::logic_error("update_dspace_refined: inconsistent container sizes");
+    auto& h = *m_handlers;
+    std::vector<Q> acts;
+    for (size_t i = 0; i < nd; ++i) acts.emplace_back(h.qr().copy(a[i]));
+    auto wp = wrap(params);
+    auto wa = wrap(acts);
+    dspace.update(wp, wa);
+    update_dimensions();
+    for (auto e : {EqnData::H, EqnData::S}) data[e].resize({m_dim.nX, m_dim.nX});
+    data[EqnData::rhs].resize({m_dim.nX, m_dim.nRHS});
+    m_d_action_norms.assign(nd, 0.0);
+    if (nd == 0) return;
+    const auto& d = m_dim;
+    const auto pp = cparamsp();
+    const auto qp = cparamsq();
+    auto& S = data[EqnData::S];
+    auto& H = data[EqnData::H];
+    CVecRef<R> rows(w.begin(), w.end());
+    rows.insert(rows.end(), a.begin(), a.end());
+    Matrix<double> g;
+    using array::fused_overlap_rows_mixed;
+    bool fused = false;
+    if constexpr (!std::is_same_v<R, Q>)
+      fused = fused_overlap_rows_mixed(h.rq(), rows, std::vector<CVecRef<R>>{w, a}, std::vector<CVecRef<Q>>{qp, rhs()}, g);
+    if (fused) {
+      const size_t cA = nd, cQ = 2 * nd, cR = cQ + d.nQ;
+      for (size_t i = 0; i < nd; ++i) {
+        for (size_t j = 0; j <= i; ++j) S(d.oD + i, d.oD + j) = S(d.oD + j, d.oD + i) = g(i, j);
+        for (size_t j = 0; j < nd; ++j) H(d.oD + i, d.oD + j) = g(i, cA + j);
+        for (size_t j = 0; j < d.nQ; ++j) {
+          S(d.oD + i, d.oQ + j) = S(d.oQ + j, d.oD + i) = g(i, cQ + j);
+          H(d.oQ + j, d.oD + i) = H(d.oD + i, d.oQ + j) = g(nd + i, cQ + j);
+        }
+        for (size_t j = 0; j < d.nRHS; ++j) data[EqnData::rhs](d.oD + i, j) = g(i, cR + j);
+        m_d_action_norms[i] = std::sqrt(std::abs(g(nd + i, cA + i)));
+      }
+    } else {
+      const auto sdd = util::overlap(w, h.rr());
+      const auto sdq = util::overlap(w, qp, h.rq());
+      const auto hdd = util::overlap(w, a, h.rr());
+      const auto hdq = util::overlap(a, qp, h.rq());
+      S.slice({d.oD, d.oD}, {d.oD + d.nD, d.oD + d.nD}) = sdd;
+      H.slice({d.oD, d.oD}, {d.oD + d.nD, d.oD + d.nD}) = hdd;
+      for (size_t i = 0; i < nd; ++i)
+        for (size_t j = 0; j < d.nQ; ++j) {
+          S(d.oD + i, d.oQ + j) = S(d.oQ + j, d.oD + i) = sdq(i, j);
+          H(d.oQ + j, d.oD + i) = H(d.oD + i, d.oQ + j) = hdq(i, j);
+        }
+      if (d.nRHS) data[EqnData::rhs].slice({d.oD, 0}, {d.oD + d.nD, d.nRHS}) = util::overlap(w, rhs(), h.rq());
+      if constexpr (!std::is_same_v<R, Q>)  // (Q = R stores its actions exactly: no error to bound)
+        for (size_t i = 0; i < nd; ++i) m_d_action_norms[i] = std::sqrt(std::abs(h.rr().dot(a[i].get(), a[i].get())));
+    }
+    if (d.nP) {  // the sparse rows: [w, a] against P in one inner product
+      const auto gp = util::overlap(rows, pp, h.rp());
+      for (size_t i = 0; i < nd; ++i)
+        for (size_t j = 0; j < d.nP; ++j) {
+          S(d.oD + i, d.oP + j) = S(d.oP + j, d.oD + i) = gp(i, j);
+          H(d.oP + j, d.oD + i) = H(d.oD + i, d.oP + j) = gp(nd + i, j);
+        }
+    }
+  }
 
   // Replaces the D space and recomputes its blocks of S and H (reference XSpace.h:174-187).
   void update_dspace(VecRef<Q>& params, VecRef<Q>& actions) {
     if (m_refined && !params.empty())
       throw std::runtime_error("refine: a D space is not supported (its stored pairs are rounded combinations)");
     dspace.update(params, actions);
+    m_d_action_norms.clear();
     update_dimensions();
     for (auto e : {EqnData::H, EqnData::S}) data[e].resize({m_dim.nX, m_dim.nX});
     auto& hqq = m_handlers->qq();
@@ -337,6 +420,7 @@ class XSpace {
   }
   void erased(size_t i) {
     dspace.erase(i);
+    if (m_refined && i < m_d_action_norms.size()) m_d_action_norms.erase(m_d_action_norms.begin() + long(i));
     remove_data(m_dim.oD + i);
     update_dimensions();
   }
@@ -449,20 +533,26 @@ class XSpace {
         // rows [params, actions] against the f64 columns [params, actions] and the stored columns
         // [Q params, rhs]: S(new, .) from the params rows, H(new, new) = params . actions, H(Q, new) from the
         // actions rows against the Q params (the products of the non-hermitian branch below), and the
-        // diagonal actions . actions for the norms; the stored Q actions are not read
+        // diagonal actions . actions for the norms; the stored Q actions are not read.  A D space
+        // (set_refined_dspace: its stored actions are true actions) adds its parameters to the stored columns
+        // and takes S(new, D), H(new, D) from the same rows as for Q.
         if (!m_hermitian || m_action_dot_action) throw std::logic_error("refine: hermitian kernels only");
-        if (d.nD != 0) throw std::runtime_error("refine: a D space is not supported");
+        if (d.nD != 0 && !m_refined_dspace) throw std::runtime_error("refine: a D space is not supported");
         CVecRef<R> rows(params.begin(), params.end());
         rows.insert(rows.end(), actions.begin(), actions.end());
         if (nn > 0 && fused_overlap_rows_mixed(h.rq(), rows, std::vector<CVecRef<R>>{params, actions},
-                                               std::vector<CVecRef<Q>>{qp, rhs()}, g)) {
-          const size_t cA = nn, cQ = 2 * nn, cR = cQ + d.nQ;
+                                               std::vector<CVecRef<Q>>{qp, dp, rhs()}, g)) {
+          const size_t cA = nn, cQ = 2 * nn, cD = cQ + d.nQ, cR = cD + d.nD;
           for (size_t i = 0; i < nn; ++i) {
             for (size_t j = 0; j <= i; ++j) qq[EqnData::S](i, j) = qq[EqnData::S](j, i) = g(i, j);
             for (size_t j = 0; j < nn; ++j) qq[EqnData::H](i, j) = g(i, cA + j);
             for (size_t j = 0; j < d.nQ; ++j) {
               qx[EqnData::S](i, d.oQ + j) = g(i, cQ + j);
               qx[EqnData::H](i, d.oQ + j) = g(nn + i, cQ + j);
+            }
+            for (size_t j = 0; j < d.nD; ++j) {
+              qx[EqnData::S](i, d.oD + j) = g(i, cD + j);
+              qx[EqnData::H](i, d.oD + j) = g(nn + i, cD + j);
             }
             for (size_t j = 0; j < m_rhs.size(); ++j) qq[EqnData::rhs](i, j) = g(i, cR + j);
             m_new_action_norms[i] = std::sqrt(std::abs(g(nn + i, cA + i)));
@@ -472,6 +562,10 @@ class XSpace {
           qx[EqnData::S].slice({0, d.oQ}, {nn, d.oQ + d.nQ}) = util::overlap(params, qp, h.rq());
           qq[EqnData::H] = util::overlap(params, actions, h.rr());
           qx[EqnData::H].slice({0, d.oQ}, {nn, d.oQ + d.nQ}) = util::overlap(actions, qp, h.rq());
+          if (d.nD) {
+            qx[EqnData::S].slice({0, d.oD}, {nn, d.oD + d.nD}) = util::overlap(params, dp, h.rq());
+            qx[EqnData::H].slice({0, d.oD}, {nn, d.oD + d.nD}) = util::overlap(actions, dp, h.rq());
+          }
           qq[EqnData::rhs] = util::overlap(params, rhs(), h.rq());
           for (size_t i = 0; i < nn; ++i)
             m_new_action_norms[i] = std::sqrt(std::abs(h.rr().dot(actions[i].get(), actions[i].get())));
@@ -557,7 +651,9 @@ class XSpace {
   bool m_hermitian = false;
   bool m_action_dot_action = false;
   bool m_refined = false;
+  bool m_refined_dspace = false;
   std::vector<double> m_q_action_norms;    // |a_j| per Q vector, Q order
+  std::vector<double> m_d_action_norms;    // |a_d| per D vector, D order (update_dspace_refined)
   std::vector<double> m_new_action_norms;  // the same of the vectors new_qspace_data was last called with
 };
 

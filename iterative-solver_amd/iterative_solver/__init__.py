@@ -47,6 +47,10 @@ REFINE_SIG = {
     "IterativeSolverHbmQuantise": (Z, [Z, PD]),
     "IterativeSolverHbmQuantiseDevice": (Z, [Z, P, Z]),
 }
+# The refined mode under a Q-space limit (option Q_REFINE_DSPACE): declared in the same way, a set of its own.
+DSPACE_SIG = {
+    "IterativeSolverHbmRefineDspaceStats": (I, [PI, PI]),
+}
 _ctx = None  # the context given to use_context
 
 
@@ -99,7 +103,7 @@ def _load():
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
             f.restype, f.argtypes = res, args
-        for name, (res, args) in {**DEVICE_SIG, **REFINE_SIG}.items():  # declared only when the library has them
+        for name, (res, args) in {**DEVICE_SIG, **REFINE_SIG, **DSPACE_SIG}.items():  # declared only when the library has them
             f = getattr(lib, name, None)
             if f is not None:
                 f.restype, f.argtypes = res, args
@@ -320,6 +324,16 @@ class IterativeSolver:
             raise RuntimeError("no active solver")
         return {"refined_actions": n.value, "first_refined_iteration": first.value, "max_delta": delta.value}
 
+    @property
+    def refine_dspace_statistics(self):
+        """With Q_REFINE_DSPACE=1: the D space's rebuilds and the actions spent on them (not among
+        refine_statistics' refined_actions)."""
+        self._check_top()
+        r, a = C.c_int(), C.c_int()
+        if _rcall("IterativeSolverHbmRefineDspaceStats", C.byref(r), C.byref(a)) != 0:
+            raise RuntimeError("no active solver")
+        return {"dspace_rebuilds": r.value, "dspace_actions": a.value}
+
     def add_value(self, value, parameters, action, sync=True):
         self._check_top()
         dev = _device_pair(self, parameters, action)
@@ -333,6 +347,14 @@ class IterativeSolver:
     def end_iteration(self, parameters, residual, sync=True):
         self._check_top()
         dev = _device_pair(self, parameters, residual)
+        # Q_REFINE_DSPACE=1: a D-space rebuild calls the refine action from inside, on this call's arrays
+        self._refine_ctx = parameters.ctx if dev is not None else None
+        try:
+            return self._end_iteration(dev, parameters, residual, sync)
+        finally:
+            self._reraise_refine()
+
+    def _end_iteration(self, dev, parameters, residual, sync):
         if dev is not None:
             return int(_dcall("IterativeSolverHbmEndIterationDevice", *dev))
         nbuffer = parameters.shape[0] if parameters.ndim > 1 else 1

@@ -24,11 +24,15 @@ EXPORTS = [
     "itsolv_davidson_dense_q32", "itsolv_davidson_synth_q32",
     # the same in the refined mode (f64 thresholds), and what the last refined solve spent
     "itsolv_davidson_dense_q32_refined", "itsolv_davidson_synth_q32_refined", "itsolv_q32_refine_stats",
+    # the refined mode under a Q-space limit (a consistent D space), and what it spent on the D space
+    "itsolv_davidson_dense_q32_refined_dspace", "itsolv_davidson_synth_q32_refined_dspace", "itsolv_q32_dspace_stats",
 ]
 # Absent from the CPU emulation of the library (loaded through this binding by patching LIB_PATH).
 OPTIONAL = frozenset(n for n in EXPORTS if n.endswith("_q32"))
 # The refined mode's entry points, optional in the same way; a set of their own: OPTIONAL stays the plain f32 Q space.
 OPTIONAL_REFINED = frozenset(n for n in EXPORTS if n.endswith("_q32_refined") or n == "itsolv_q32_refine_stats")
+# The refined mode's consistent D space, optional in the same way; again a set of its own.
+OPTIONAL_DSPACE = frozenset(n for n in EXPORTS if n.endswith("_q32_refined_dspace") or n == "itsolv_q32_dspace_stats")
 
 # Diagonal families of the synthetic H (include/subspace_hip.h sspx_synth, itsolv_hbm/problems.h).
 DIAG_LINEAR, DIAG_BOUNDED = 0, 1
@@ -164,9 +168,12 @@ def load_library():
             "itsolv_davidson_dense_q32_refined": (I, [P, PD, Z, PO, PF, PR, PD]),
             "itsolv_davidson_synth_q32_refined": (I, [P, Z, C.POINTER(Synth), PO, PF, PR, PD]),
             "itsolv_q32_refine_stats": (I, [PI, PI, PD]),
+            "itsolv_davidson_dense_q32_refined_dspace": (I, [P, PD, Z, PO, PF, PR, PD]),
+            "itsolv_davidson_synth_q32_refined_dspace": (I, [P, Z, C.POINTER(Synth), PO, PF, PR, PD]),
+            "itsolv_q32_dspace_stats": (I, [PI, PI]),
         }
         for name, (res, args) in sig.items():
-            if (name in OPTIONAL or name in OPTIONAL_REFINED) and not hasattr(L, name):
+            if (name in OPTIONAL or name in OPTIONAL_REFINED or name in OPTIONAL_DSPACE) and not hasattr(L, name):
                 continue
             f = getattr(L, name)
             f.restype = res
@@ -175,14 +182,16 @@ def load_library():
     return _lib
 
 
-def _entry(name: str, q32: bool, refine: bool = False):
+def _entry(name: str, q32: bool, refine: bool = False, refine_dspace: bool = False):
     """The solver entry point `name`, or with q32 its form over a Q space stored in f32 (refine: in the
-    refined mode)."""
+    refined mode; refine_dspace: with its consistent D space, which admits max_size_qspace)."""
     if refine and not q32:
         raise ValueError("refine=True needs q32=True: the refined mode is a mode of the f32 Q space")
+    if refine_dspace and not refine:
+        raise ValueError("refine_dspace=True needs refine=True: the consistent D space is part of the refined mode")
     if not q32:
         return getattr(load_library(), name)
-    full = name + ("_q32_refined" if refine else "_q32")
+    full = name + ("_q32_refined_dspace" if refine_dspace else "_q32_refined" if refine else "_q32")
     f = getattr(load_library(), full, None)
     if f is None:
         raise sh.SspError(7, f"{full}: the loaded library has no f32 Q space")
@@ -204,6 +213,12 @@ def _refine_stats() -> dict:
     return {"refined_actions": a.value, "first_refined_iteration": f.value, "max_delta": d.value}
 
 
+def _dspace_stats() -> dict:
+    r, a = C.c_int(), C.c_int()
+    load_library().itsolv_q32_dspace_stats(C.byref(r), C.byref(a))
+    return {"dspace_rebuilds": r.value, "dspace_actions": a.value}
+
+
 def _call(fn, args, nout):
     res = Result()
     out = np.zeros(max(1, nout))
@@ -218,11 +233,13 @@ def _call(fn, args, nout):
 def davidson_synthetic(ctx: sh.Context, n: int, rho: float, rank: int, seed: int, n_local: int | None = None,
                        solutions: bool = True, *, diag_kind: int = DIAG_LINEAR, alpha: float = 0.0,
                        target: float = 1.0, q32: bool = False, refine: bool = False, kappa: float | None = None,
-                       **opts):
+                       refine_dspace: bool = False, **opts):
     """q32: the Q space is stored in f32 (half the HBM and bytes of every pass over it; arithmetic in f64).
     refine (with q32): the refined mode, which reaches f64 thresholds at the price of one more action per
-    refined root and iteration (include/itsolv_hbm.h); the result then has "refine" (its statistics)."""
-    fn = _entry("itsolv_davidson_synth", q32, refine)
+    refined root and iteration (include/itsolv_hbm.h); the result then has "refine" (its statistics).
+    refine_dspace (with refine): the refined mode under max_size_qspace, its D space rebuilt consistently at
+    nD <= nroots more actions per rebuild; the result then has "refine_dspace" (rebuilds and their actions)."""
+    fn = _entry("itsolv_davidson_synth", q32, refine, refine_dspace)
     o = make_options(**opts)
     nl = n if n_local is None else n_local
     spec = Synth(rho, rank, seed, diag_kind, alpha, target)
@@ -230,15 +247,17 @@ def davidson_synthetic(ctx: sh.Context, n: int, rho: float, rank: int, seed: int
                    o.nroots * nl if solutions else 0)
     if refine:
         r["refine"] = _refine_stats()
+    if refine_dspace:
+        r["refine_dspace"] = _dspace_stats()
     if solutions:
         r["solutions"] = sol[: o.nroots * nl].reshape(o.nroots, nl)
     return r
 
 
 def davidson_dense(ctx: sh.Context, h: np.ndarray, q32: bool = False, refine: bool = False,
-                   kappa: float | None = None, **opts):
-    """q32: the Q space is stored in f32 (arithmetic in f64); refine: as davidson_synthetic's."""
-    fn = _entry("itsolv_davidson_dense", q32, refine)
+                   kappa: float | None = None, refine_dspace: bool = False, **opts):
+    """q32: the Q space is stored in f32 (arithmetic in f64); refine, refine_dspace: as davidson_synthetic's."""
+    fn = _entry("itsolv_davidson_dense", q32, refine, refine_dspace)
     h = np.ascontiguousarray(h, dtype=np.float64)
     n = h.shape[0]
     o = make_options(**opts)
@@ -246,6 +265,8 @@ def davidson_dense(ctx: sh.Context, h: np.ndarray, q32: bool = False, refine: bo
                    + _refine_args(refine, kappa), o.nroots * n)
     if refine:
         r["refine"] = _refine_stats()
+    if refine_dspace:
+        r["refine_dspace"] = _dspace_stats()
     r["solutions"] = sol[: o.nroots * n].reshape(o.nroots, n)
     return r
 

@@ -60,6 +60,8 @@ EXPORTS = [
     "ssp_rows_import", "ssp_rows_export",
     # the export that rounds its first rows through f32 (the refined f32 Q space of the RC API)
     "ssp_rows_export_quantised",
+    # new f32 vectors with their f64 twins (the consistent D space of the refined f32 Q space)
+    "ssp_q32_combine_widen",
 ]
 
 # The mixed-precision entry points are optional in a loaded library: the CPU emulation of the f64 C ABI
@@ -70,7 +72,9 @@ OPTIONAL_REFINED = frozenset({"ssp_quantise_f32"})
 OPTIONAL = frozenset(n for n in EXPORTS if n.endswith("_f32") or n.startswith("ssp_mx_")) - OPTIONAL_REFINED
 # The fused passes over an f32 Q space are tolerated in the same way (absent from the emulation, a call
 # raises SspError(SSP_ERR_UNSUPPORTED)); they are a set of their own: OPTIONAL stays the storage layer.
-OPTIONAL_Q32 = frozenset(n for n in EXPORTS if n.startswith("ssp_q32_"))
+# The combine-and-widen pass of the refined mode's D space, optional in the same way; again a set of its own.
+OPTIONAL_DSPACE = frozenset({"ssp_q32_combine_widen"})
+OPTIONAL_Q32 = frozenset(n for n in EXPORTS if n.startswith("ssp_q32_")) - OPTIONAL_DSPACE
 # The row-block entry points (a caller's device block <-> library vectors), optional in the same way and a
 # set of their own: the three sets above stay what they were.
 OPTIONAL_ROWS = frozenset({"ssp_rows_import", "ssp_rows_export"})
@@ -205,11 +209,12 @@ def _declare(lib):
         "ssp_q32_gemm_inner_cols": (I, [P, P, PD, I, P, C.POINTER(I), PD, I, Z, PD]),
         "ssp_q32_construct_solution": (I, [P, PD, PZ, PZ, PD, I, PD, P, I, P, I, Z, Z]),
         "ssp_q32_block_update": (I, [P, PD, PZ, PZ, PD, I, PD, P, I, P, PD, I, Z, Z]),
+        "ssp_q32_combine_widen": (I, [P, PD, P, I, P, P, I, Z]),
         "ssp_rows_import": (I, [P, P, Z, P, I, Z]),
         "ssp_rows_export": (I, [P, P, PD, I, P, Z, Z]),
         "ssp_rows_export_quantised": (I, [P, P, PD, I, I, P, Z, Z]),
     }
-    optional = OPTIONAL | OPTIONAL_Q32 | OPTIONAL_REFINED | OPTIONAL_ROWS | OPTIONAL_ROWS_Q
+    optional = OPTIONAL | OPTIONAL_Q32 | OPTIONAL_REFINED | OPTIONAL_ROWS | OPTIONAL_ROWS_Q | OPTIONAL_DSPACE
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -948,6 +953,18 @@ class Context:
         n = rows[0].n if m else (cols[0].n if k else 0)
         _check(f(self.handle, _ptrs(rows), _dptr(a), m, _ptrs(cols), ty, _dptr(b), k, n, _dptr(out)))
         return out
+
+    def q32_combine_widen(self, alphas, xx, yy, ww):
+        """yy[j] = float32(sum_i alphas[i, j] xx[i]) and ww[j] = float64(yy[j]) in one write-only pass:
+        float32 sources xx and destinations yy, float64 twins ww (ssp_q32_combine_widen)."""
+        f = self._mx("ssp_q32_combine_widen")
+        if any(_code(v) != SSP_F32 for v in list(xx) + list(yy)) or any(_code(v) != SSP_F64 for v in ww):
+            raise TypeError("q32_combine_widen: float32 sources and destinations, float64 twins")
+        if len(ww) != len(yy):
+            raise ValueError("q32_combine_widen: one twin per destination")
+        al = np.ascontiguousarray(alphas, dtype=np.float64).reshape(len(xx), len(yy))
+        n = yy[0].n if yy else 0
+        _check(f(self.handle, _dptr(al), _ptrs(xx), len(xx), _ptrs(yy), _ptrs(ww), len(yy), n))
 
     @staticmethod
     def _f32_sources(xx, what):
