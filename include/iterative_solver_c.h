@@ -195,13 +195,22 @@ void IterativeSolverHbmDiagonalsDevice(double* diagonals);
  *                   the plain solver, a rebuild in every iteration once the Q space is full.  With a limit under
  *                   about 8 nroot the mode may stall short of an f64 threshold (near 1e-10 |H|).
  * Refused, each with an error that names the option (recorded, not thrown, after IterativeSolverHbmSetThrow(0)):
- * an unknown Q_STORAGE value; either option on LinearEquations, NonLinearEquations, Optimize or RSPT; either
+ * an unknown Q_STORAGE value; either option on NonLinearEquations, Optimize or RSPT; either
  * option on an instance with more than one rank; Q_REFINE with hermitian = 0, MAX_SIZE_QSPACE, RESET_D or
  * RESET_D_MAX_Q_SIZE (the refined mode has no D space); Q_STORAGE=f32 over a vector library without the
  * mixed-precision ABI.  Out of scope: multi-rank f32 instances, a D space or a Q-space limit in refined mode
  * without Q_REFINE_DSPACE=1, the D-space reset in refined mode,
- * f32 Q for the other solver families, a Fortran binding of the refine callback (the Fortran module passes
+ * f32 Q for DIIS and the optimisers, a Fortran binding of the refine callback (the Fortran module passes
  * `options` through, so the plain Q_STORAGE=f32 works from Fortran), a device-side apply_on_p.
+ *
+ * Linear equations.  IterativeSolverLinearEquationsInitialize accepts Q_STORAGE=f32 and, with it, Q_REFINE=1 and
+ * Q_REFINE_KAPPA (one rank, "Davidson").  Plain: the right-hand sides are stored rounded with the Q space, so the
+ * true residual cannot fall below about 2^-24 |b|: thresholds down to about 1e-6.  Refined: the instance keeps an
+ * f64 twin of every right-hand side, which the subspace and the residuals read instead; the refine action, the
+ * rounded rows of EndIteration and the statistics are the ones described here, and the reported errors are true
+ * relative residuals down to f64 thresholds.  Refused by name: Q_REFINE=1 without Q_STORAGE=f32 (with the Q space
+ * in f64 the residuals are exact already), Q_REFINE_DSPACE, and in refined mode hermitian = 0, MAX_SIZE_QSPACE,
+ * RESET_D, RESET_D_MAX_Q_SIZE and aughes > 0 (the augmented Hessian's residual is not A x - b).
  *
  * The refine action.  fn(nvec, parameters, action, ld, user) must set action row k = H * parameters row k for
  * k < nvec (row k at p + k*ld).  It is called from inside IterativeSolverAddVector, its device form and

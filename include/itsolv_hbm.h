@@ -177,6 +177,37 @@ int itsolv_q32_dspace_stats(int* rebuilds, int* actions);
  * x_out (nrhs x n, host) may be NULL. */
 int itsolv_linear_equations_dense(ssp_ctx* ctx, const double* a, size_t n, const double* rhs, int nrhs,
                                   const itsolv_options* opt, itsolv_result* out, double* x_out);
+/* The same solver at scale: A is the synthetic H of sspx_synth (symmetric positive definite for rho >= 0;
+ * action, diagonal and preconditioner on the device, as itsolv_davidson_synth's), sharded over the ranks of
+ * ctx in the same way, and the right-hand sides are b_r = sspx_fill_random(seed = rhs_seed, vec = r) at the
+ * shard's global offset, r < nrhs <= ITSOLV_MAX_ROOTS.  residual_norms are |A x_r - b_r| / |b_r| recomputed
+ * from the action; x_out (nrhs x the local length, host) may be NULL. */
+int itsolv_linear_equations_synth(ssp_ctx* ctx, size_t n, const sspx_synth* spec, int nrhs, unsigned long long rhs_seed,
+                                  const itsolv_options* opt, itsolv_result* out, double* x_out);
+/* Linear equations with the Q space stored in f32 (one rank).
+ *   *_q32          plain: the right-hand sides are stored rounded with the Q space, so the true residual cannot
+ *                  fall below about 2^-24 |b|: meaningful down to thresholds of about 1e-6, as the plain f32
+ *                  eigensolver.  Every option of the f64 solver is allowed.
+ *   *_q32_refined  the refined mode (itsolv_davidson_*_q32_refined): new parameters quantised before their
+ *                  action, H rows from f64 actions, an f64 twin of every right-hand side beside the stored one
+ *                  (the subspace rhs rows and the residuals read the twin only), and residuals recomputed from
+ *                  the action of the solution where the bound delta_i = 2^-24 sum_j |c_ji| |a_j| / |b_i| no
+ *                  longer vouches for the estimate.  It reaches f64 thresholds at one more action per refined
+ *                  root and iteration; the reported errors are then true relative residuals.  Scope: hermitian = 1,
+ *                  max_size_qspace, reset_D and reset_D_max_Q_size unset, augmented_hessian = 0; anything else
+ *                  is an error naming the option.  refine may be NULL (kappa = 8); itsolv_q32_refine_stats
+ *                  reports what the solve spent. */
+int itsolv_linear_equations_dense_q32(ssp_ctx* ctx, const double* a, size_t n, const double* rhs, int nrhs,
+                                      const itsolv_options* opt, itsolv_result* out, double* x_out);
+int itsolv_linear_equations_synth_q32(ssp_ctx* ctx, size_t n, const sspx_synth* spec, int nrhs,
+                                      unsigned long long rhs_seed, const itsolv_options* opt, itsolv_result* out,
+                                      double* x_out);
+int itsolv_linear_equations_dense_q32_refined(ssp_ctx* ctx, const double* a, size_t n, const double* rhs, int nrhs,
+                                              const itsolv_options* opt, const itsolv_q32_refine* refine,
+                                              itsolv_result* out, double* x_out);
+int itsolv_linear_equations_synth_q32_refined(ssp_ctx* ctx, size_t n, const sspx_synth* spec, int nrhs,
+                                              unsigned long long rhs_seed, const itsolv_options* opt,
+                                              const itsolv_q32_refine* refine, itsolv_result* out, double* x_out);
 /* OptimizeBFGS (algorithm 0) or OptimizeSD (1) minimising the Rayleigh quotient x.Hx / x.x of a
  * dense row-major H (HBM, single rank) from x = e_0; eigenvalues[0] = final function value, x_out
  * (n, host) may be NULL. */

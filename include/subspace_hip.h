@@ -375,6 +375,26 @@ int ssp_mx_gemm_inner(ssp_ctx* ctx, const void* const* xx, ssp_dtype tx, const d
  * (ssp_gemm_outer_set).  No destination may alias a source. */
 int ssp_mx_gemm_outer(ssp_ctx* ctx, const double* alphas, const void* const* xx, ssp_dtype tx, const double* xs, int k,
                       void* const* yy, ssp_dtype ty, int m, size_t n, int set);
+/* Residuals against right-hand sides, and their norms, in one pass (LinearEquationsDavidson's
+ * construct_residual + update_errors, reference LinearEquationsDavidson.h:175-186 and
+ * IterativeSolverTemplate.h:95-102; the linear-equations twin of ssp_axpy_pairs_norm):
+ *   yy[j][:] = s[j] * (ys[j] * yy[j][:] - (double)bb[j][:]),  out[j] = <yy[j], yy[j]> summed over ranks
+ * bb is stored as tb (SSP_F32: the stored right-hand sides of an f32 Q space; SSP_F64: the f64 twins of its
+ * refined mode), yy is f64.  ys is the pending scale of yy, applied as yy is loaded (the one rounding an eager
+ * ssp_scal stores); it may be null (all 1).  The subtraction is rounded once and the product with s once, with
+ * no contraction, so yy is bit-identical to ssp_scal(ys[j]) (where ys[j] != 1), ssp_mx_axpy(-1, bb[j], yy[j])
+ * and ssp_scal(s[j]) on the same context -- three launches per vector and a dot, 44 or 48 bytes per element
+ * where this pass moves 20 or 24.
+ *   - One launch serves m <= 16; more vectors take that unfused sequence and one ssp_dot each.
+ *   - The norms are fixed-order sums (per-workgroup partials on a fixed grid, folded by the last workgroup):
+ *     repeated calls give the same bits.  On vectors of at most exact_max elements they are the reference's
+ *     sequential dots of the unfused sequence, in one reduction.
+ *   - With a communicator attached the buffer summed over ranks has length m whatever n is (m <= 16); n = 0
+ *     writes zeros; m = 0 returns at once.  Pending zero fills are stored first.
+ *   - Every pointer 16-byte aligned and non-null (n > 0); no yy[j] may be a bb[i] or another yy[i].
+ * Ledger name rhs_residual_norms, bytes n m (16 + 4 or 8). */
+int ssp_mx_rhs_residual_norms(ssp_ctx* ctx, const void* const* bb, ssp_dtype tb, const double* s, double* const* yy,
+                              const double* ys, int m, size_t n, double* out);
 
 /* ---- fused solver passes over an f32 Q space beside f64 R vectors (itsolv_hbm/hbm_handlers_f32.h):
  *      the mixed-precision rule above, applied per column / per source.

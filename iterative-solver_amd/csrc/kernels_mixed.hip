@@ -12,6 +12,7 @@
 // kernel moves 512 N.
 //
 // Kernels.  k_mx_copy, k_mx_axpy, k_mx_scal, k_mx_dot: one per-element operation each, over map_quads;
+// k_mx_rhs_residual_norms<TB, K> (y_j = s_j (ys_j y_j - b_j) with b stored as TB, and <y_j, y_j>, up to 16 pairs per launch);
 // k_quantise_f32 (f64 vectors rounded through f32 in place, up to 16 per launch); k_mx_fill; k_mx_outer<TX, TY, M, SET, TWIN> (gemm_outer, launched chunk by chunk from outer_chunks, also the
 // dense pass of the ssp_q32_* updates; TWIN: ssp_q32_combine_widen's second store of every result, widened); k_mx_inner<TX, CP, MG, NG> (gemm_inner: the one MFMA tile kernel,
 // CP the columns' storage -- float, double, or ByGroup for ssp_q32_gemm_inner_cols).  with_pair maps the
@@ -200,6 +201,94 @@ __global__ __launch_bounds__(kBlock) void k_mx_dot(const TX* __restrict__ x, con
   const double s = ssp::block_sum256((acc[0] + acc[1]) + (acc[2] + acc[3]));
   if (threadIdx.x == 0) ssp::store_partial(partial + blockIdx.x, s);
   ssp::fold_tail(partial, tail);
+}
+
+// ---- residuals against a right-hand side, and their norms ---------------------------------------------
+struct RhsResidualArgs {
+  const void* b[ssp::kOuterDst];
+  double* y[ssp::kOuterDst];
+  double s[ssp::kOuterDst];
+  double ys[ssp::kOuterDst];
+  int m;
+  size_t n;
+  double* partial;     // [gridDim.x][m]; null: the residuals only (the exact path forms the norms itself)
+  ssp::FoldTail tail;  // the fused fold (with partial)
+};
+
+// One element: y * ys (the rounding an eager scal stores), the subtraction rounded once -- what
+// fma(-1, b, y) gives, its product being exact -- then the product with s rounded once.  No contraction.
+__device__ __forceinline__ double rhs_residual(double yv, double ys, double bv, double s) {
+#pragma clang fp contract(off)
+  return (yv * ys - bv) * s;
+}
+
+// The lane's U quads p0 + 64 u of one pair: the quads of b (as stored) and of y are all in flight before the
+// first result is formed; acc takes the lane's squares in element order.
+template <int U, bool NT, typename TB>
+__device__ __forceinline__ void rhs_residual_at(const TB* b, double* y, double s, double ys, size_t p0, double& acc) {
+  Raw<TB> bv[U];
+  Raw<double> yv[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) bv[u] = ldq<NT>(b + 4 * (p0 + 64 * u));
+#pragma unroll
+  for (int u = 0; u < U; ++u) yv[u] = ldq<NT>(static_cast<const double*>(y) + 4 * (p0 + 64 * u));
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    double w[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      w[e] = rhs_residual(yv[u].get(e), ys, bv[u].get(e), s);
+      acc = fma(w[e], w[e], acc);
+    }
+    stq<NT>(y + 4 * (p0 + 64 * u), w);
+  }
+}
+
+// y_j = s_j (ys_j y_j - (double)b_j) and the per-workgroup partials of <y_j, y_j>, j < m, in one launch: the
+// workgroup takes the pairs one after the other, each over the windows of for_quads (the f32 and f64 elements of
+// a position meet in one lane; 4 KiB of an f32 b and 8 KiB of y in flight per wave visit), with one accumulator
+// per lane -- the register footprint of one pair whatever m is (all m pairs per window visit, the shape of
+// k_axpy_pairs_norm, takes the 255 registers and spills from m = 16 with an f64 quad per operand).  The pair's
+// pointers and scales are wave-uniform reads through the constant address space.  The last workgroup to arrive
+// folds the partials in fixed order (K: outputs per trip of the fold).
+template <typename TB, int K>
+__global__ __launch_bounds__(kBlock) void k_mx_rhs_residual_norms(const RhsResidualArgs a) {
+  using cchar = const __attribute__((address_space(4))) char;
+  using cdouble = const __attribute__((address_space(4))) double;
+  typedef const void* cvoidp;
+  typedef double* doublep;
+  cchar* const karg = (cchar*)__builtin_amdgcn_kernarg_segment_ptr();
+  __shared__ double red[kBlock / 64][ssp::kOuterDst];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll 1
+  for (int j = 0; j < a.m; ++j) {
+    const TB* const b = static_cast<const TB*>(((const __attribute__((address_space(4))) cvoidp*)(karg + offsetof(RhsResidualArgs, b)))[j]);
+    double* const y = ((const __attribute__((address_space(4))) doublep*)(karg + offsetof(RhsResidualArgs, y)))[j];
+    const double s = ((cdouble*)(karg + offsetof(RhsResidualArgs, s)))[j];
+    const double ys = ((cdouble*)(karg + offsetof(RhsResidualArgs, ys)))[j];
+    double acc = 0;
+    for_quads<kMxU>(
+        a.n, [&](size_t p0) { rhs_residual_at<kMxU, true>(b, y, s, ys, p0, acc); },
+        [&](size_t p) { rhs_residual_at<1, false>(b, y, s, ys, p, acc); },
+        [&](size_t i) {
+          const double w = rhs_residual(y[i], ys, double(b[i]), s);
+          y[i] = w;
+          acc = fma(w, w, acc);
+        });
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if (lane == 0) red[wave][j] = acc;
+  }
+  if (!a.partial) return;
+  // per-workgroup sums into partial[block][m] (kernels_panel.hip block_partials), then the fused fold
+  __syncthreads();
+  if (int(threadIdx.x) < a.m) {
+    double t = red[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < kBlock / 64; ++w) t += red[w][threadIdx.x];
+    ssp::store_partial(a.partial + size_t(blockIdx.x) * a.m + threadIdx.x, t);
+  }
+  ssp::fold_tail<K>(a.partial, a.tail);
 }
 
 // ---- quantise -------------------------------------------------------------------------------------
@@ -993,6 +1082,73 @@ int ssp_mx_dot(ssp_ctx* ctx, const void* x, ssp_dtype tx, const void* y, ssp_dty
       SSP_LAUNCH((k_mx_dot<TX, TY>), g, b, 0, ctx->stream, static_cast<const TX*>(x), static_cast<const TY*>(y), n,
                  ctx->partial, tail);
     }));
+  }
+  return ssp::fold_finish(ctx, tail, out);
+}
+
+int ssp_mx_rhs_residual_norms(ssp_ctx* ctx, const void* const* bb, ssp_dtype tb, const double* s, double* const* yy,
+                              const double* ys, int m, size_t n, double* out) {
+  SSP_CHECK_CTX(ctx);  // pending zero fills are stored: every operand is read
+  if (bad_dtype(tb)) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_rhs_residual_norms: bad dtype");
+  if (m < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_rhs_residual_norms: negative dimension");
+  if (m == 0) return SSP_OK;
+  if (!s || !out) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_rhs_residual_norms: null scales or out");
+  SSP_TRY(check_ptrs(bb, m, n, "ssp_mx_rhs_residual_norms"));
+  SSP_TRY(check_ptrs(reinterpret_cast<const void* const*>(yy), m, n, "ssp_mx_rhs_residual_norms"));
+  for (int j = 0; n > 0 && j < m; ++j)
+    for (int i = 0; i < m; ++i)
+      if (static_cast<const void*>(yy[j]) == bb[i] || (i < j && yy[i] == yy[j]))
+        return ssp::set_error(SSP_ERR_ARG, "ssp_mx_rhs_residual_norms: a destination aliases another operand");
+  if (m > ssp::kOuterDst) {  // more than one launch: the unfused sequence, same values (at every n: one
+                             // reduction per vector on every rank)
+    for (int j = 0; j < m; ++j) {
+      if (ys && ys[j] != 1.0) SSP_TRY(ssp_scal(ctx, ys[j], yy[j], n));
+      SSP_TRY(ssp_mx_axpy(ctx, -1.0, bb[j], tb, yy[j], SSP_F64, n));
+      SSP_TRY(ssp_scal(ctx, s[j], yy[j], n));
+    }
+    for (int j = 0; j < m; ++j) SSP_TRY(ssp_dot(ctx, yy[j], yy[j], n, out + j));
+    return SSP_OK;
+  }
+  if (n == 0) {  // an empty shard: zeros, in the one buffer of length m every other path reduces
+    SSP_TRY(ssp::ensure_result(ctx, size_t(m)));
+    SSP_TRY_HIP(hipMemsetAsync(ctx->result_dev, 0, size_t(m) * sizeof(double), ctx->stream));
+    return ssp::reduce_fetch(ctx, out, size_t(m));
+  }
+  const bool exact = ssp::exact_mode(ctx, n);
+  const unsigned grid = quad_grid(ctx, n, kMxU, unsigned(ctx->fused_per_cu));
+  RhsResidualArgs a{};
+  a.m = m;
+  a.n = n;
+  for (int j = 0; j < m; ++j) {
+    a.b[j] = bb[j];
+    a.y[j] = yy[j];
+    a.s[j] = s[j];
+    a.ys[j] = ys ? ys[j] : 1.0;
+  }
+  ssp::FoldTail tail{};
+  SSP_TRY(ssp::fold_begin(ctx, m, &tail));
+  {
+    ssp::LedgerScope ls(ctx, "rhs_residual_norms", (16.0 + esize(tb)) * n * m);
+    if (!exact) {
+      SSP_TRY(ssp::ensure_partial(ctx, size_t(grid) * m));
+      a.partial = ctx->partial;
+      a.tail = tail;
+    }
+    const dim3 g(grid), b(kBlock);
+    const auto launch = [&](auto B) {
+      using TB = decltype(B);
+      if (m <= 1) SSP_LAUNCH((k_mx_rhs_residual_norms<TB, 1>), g, b, 0, ctx->stream, a);
+      else if (m <= 4) SSP_LAUNCH((k_mx_rhs_residual_norms<TB, 4>), g, b, 0, ctx->stream, a);
+      else SSP_LAUNCH((k_mx_rhs_residual_norms<TB, 8>), g, b, 0, ctx->stream, a);
+    };
+    if (tb == SSP_F32) launch(float());
+    else launch(double());
+    SSP_TRY_HIP(hipGetLastError());
+    // short vectors: every element above is the unfused sequence's (each operation rounded once, in either
+    // arithmetic); the norms are the reference's sequential dots, one reduction for all of them
+    if (exact)
+      SSP_TRY(ssp::exact_inner(ctx, const_cast<const double* const*>(yy), nullptr, m,
+                               const_cast<const double* const*>(yy), nullptr, m, n, true, tail));
   }
   return ssp::fold_finish(ctx, tail, out);
 }

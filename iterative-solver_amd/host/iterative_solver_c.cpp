@@ -42,6 +42,7 @@ const auto rows_import_fn = &ssp_rows_import;
 const auto rows_export_fn = &ssp_rows_export;
 const auto rows_export_q_fn = &ssp_rows_export_quantised;
 const auto make_q32_fn = &itsolv_rc::make_rc_davidson_q32;  // null without host_q32/ (rc_solver.h)
+const auto make_lineq_q32_fn = &itsolv_rc::make_rc_linear_equations_q32;  // the same
 
 using Solver = it::IterativeSolverTemplate<Vec, Vec, SparseP>;
 using Davidson = it::LinearEigensystemDavidson<Vec, Vec, SparseP>;
@@ -470,12 +471,23 @@ void IterativeSolverLinearEquationsInitialize(size_t n, size_t nroot, size_t* ra
                                               const char* algorithm, const char* options) {
   guarded([&] {
     (void)fname;
-    refuse_q_options(options, "LinearEquations");
-    auto handlers = molpro::linalg::hbm::make_handlers();
-    auto made = it::create_LinearEquations(algorithm ? algorithm : "", options ? options : "", handlers);
-    std::unique_ptr<LinEq> solver(static_cast<LinEq*>(made.release()));
+    // extension: Q_STORAGE=f32, and with it Q_REFINE=1 and Q_REFINE_KAPPA (one rank, "Davidson").  Q_REFINE=1
+    // alone stays refused: with the Q space in f64 the residuals are exact already.
+    const auto q = q_options(options);
+    const std::string method = algorithm ? algorithm : "";
+    if (q.dspace) throw std::invalid_argument("Q_REFINE_DSPACE: not available for LinearEquations");
+    if (q.refine && !q.f32)
+      throw std::invalid_argument("Q_REFINE: not available for LinearEquations unless Q_STORAGE=f32 (with the Q space "
+                                  "in f64 the residuals are exact already)");
+    if (q.f32 && !(method == "Davidson" || method.empty()))
+      throw std::invalid_argument("Q_STORAGE=f32: available for the LinearEquations Davidson only, not " + method);
+    if (q.f32 && !make_lineq_q32_fn)
+      throw std::logic_error("Q_STORAGE=f32: SSP_ERR_UNSUPPORTED: not available for LinearEquations here: the loaded "
+                             "vector library has no mixed-precision ABI");
     Instance in;
     in.dev = make_device(fcomm);
+    if (q.f32 && in.dev->nranks() > 1)
+      throw std::invalid_argument("Q_STORAGE=f32: LinearEquations: not available on an instance with more than one rank");
     setup(in, n, range_begin, range_end);
     // reference IterativeSolverCMPI.cpp:199-225: rhs as R vectors, then options
     std::vector<Vec> b;
@@ -483,6 +495,17 @@ void IterativeSolverLinearEquationsInitialize(size_t n, size_t nroot, size_t* ra
       b.emplace_back(in.dev, n);
       check(ssp_upload(in.dev->ctx(), b.back().data_wo(), rhs + r * n + in.offset, in.local), "ssp_upload");
     }
+    if (q.f32) {  // the same construction over make_handlers_q32() (host_q32/rc_q32.cpp)
+      in.solver = make_lineq_q32_fn(options ? options : "", b, hermitian != 0, aughes, q.refine ? &q.kappa : nullptr);
+      in.solver->set_convergence_threshold(thresh);
+      in.solver->set_convergence_threshold_value(thresh_value);
+      in.solver->set_verbosity(verbosity_of(verbosity));
+      push(std::move(in));
+      return;
+    }
+    auto handlers = molpro::linalg::hbm::make_handlers();
+    auto made = it::create_LinearEquations(algorithm ? algorithm : "", options ? options : "", handlers);
+    std::unique_ptr<LinEq> solver(static_cast<LinEq*>(made.release()));
     solver->set_hermiticity(hermitian != 0);
     solver->set_n_roots(nroot);
     solver->add_equations(b);

@@ -152,5 +152,12 @@ class RcSolverOf final : public RcSolver {
 // parsed as create_LinearEigensystem parses them.  Weak: null without host_q32/.
 std::unique_ptr<RcSolver> make_rc_davidson_q32(const std::string& options, size_t nroot, bool hermitian)
     __attribute__((weak));
+// LinearEquations "Davidson" over the same handlers, for the right-hand sides rhs (R vectors), set up as
+// IterativeSolverLinearEquationsInitialize sets up the f64 solver.  refine_kappa: null for the plain f32 Q space;
+// else the refined mode with that kappa, set before the equations are added (it keeps their twins in R's
+// format) and its scope checked once everything is set (errors name the option).  Weak: null without host_q32/.
+std::unique_ptr<RcSolver> make_rc_linear_equations_q32(const std::string& options, std::vector<Vec>& rhs, bool hermitian,
+                                                       double augmented_hessian, const double* refine_kappa)
+    __attribute__((weak));
 
 }  // namespace itsolv_rc

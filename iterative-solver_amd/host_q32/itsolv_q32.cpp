@@ -101,6 +101,46 @@ int itsolv_davidson_dense_q32_refined_dspace(ssp_ctx* ctx, const double* h, size
   return dense_q32(ctx, h, n, opt, &kappa, out, solutions_out, true);
 }
 
+// Linear equations over the f32 Q space: plain (the right-hand sides stored rounded with the Q space; meaningful
+// down to about 1e-6) and refined (f64 twins of the right-hand sides, refined residuals: f64 thresholds).
+int itsolv_linear_equations_dense_q32(ssp_ctx* ctx, const double* a, size_t n, const double* rhs, int nrhs,
+                                      const itsolv_options* opt, itsolv_result* out, double* x_out) {
+  return guarded([&] {
+    linear_equations_dense<VecF32>(ctx, a, n, rhs, nrhs, molpro::linalg::hbm::make_handlers_q32(), opt, out, x_out);
+  });
+}
+
+int itsolv_linear_equations_synth_q32(ssp_ctx* ctx, size_t n, const sspx_synth* spec, int nrhs,
+                                      unsigned long long rhs_seed, const itsolv_options* opt, itsolv_result* out,
+                                      double* x_out) {
+  return guarded([&] {
+    linear_equations_synth<VecF32>(ctx, n, spec, nrhs, rhs_seed, molpro::linalg::hbm::make_handlers_q32(), opt, out,
+                                   x_out);
+  });
+}
+
+int itsolv_linear_equations_dense_q32_refined(ssp_ctx* ctx, const double* a, size_t n, const double* rhs, int nrhs,
+                                              const itsolv_options* opt, const itsolv_q32_refine* refine,
+                                              itsolv_result* out, double* x_out) {
+  g_refine_stats = pr::RefineStats{};
+  const double kappa = kappa_of(refine);
+  return guarded([&] {
+    linear_equations_dense<VecF32>(ctx, a, n, rhs, nrhs, molpro::linalg::hbm::make_handlers_q32(), opt, out, x_out,
+                                   &kappa, &g_refine_stats);
+  });
+}
+
+int itsolv_linear_equations_synth_q32_refined(ssp_ctx* ctx, size_t n, const sspx_synth* spec, int nrhs,
+                                              unsigned long long rhs_seed, const itsolv_options* opt,
+                                              const itsolv_q32_refine* refine, itsolv_result* out, double* x_out) {
+  g_refine_stats = pr::RefineStats{};
+  const double kappa = kappa_of(refine);
+  return guarded([&] {
+    linear_equations_synth<VecF32>(ctx, n, spec, nrhs, rhs_seed, molpro::linalg::hbm::make_handlers_q32(), opt, out,
+                                   x_out, &kappa, &g_refine_stats);
+  });
+}
+
 int itsolv_q32_dspace_stats(int* rebuilds, int* actions) {
   if (rebuilds) *rebuilds = g_refine_stats.dspace_rebuilds;
   if (actions) *actions = g_refine_stats.dspace_actions;

@@ -1,6 +1,6 @@
 // Q_STORAGE=f32 of the reverse-communication C API (include/iterative_solver_c.h): the instance's solver as
-// LinearEigensystemDavidson<Vec, VecF32, SparseP> over make_handlers_q32(), behind the Q-independent face of
-// host/rc_solver.h.  It lives here, not in host/, for the reason host_q32/itsolv_q32.cpp does: the handlers
+// LinearEigensystemDavidson<Vec, VecF32, SparseP> or LinearEquationsDavidson<Vec, VecF32, SparseP> over
+// make_handlers_q32(), behind the Q-independent face of host/rc_solver.h.  It lives here, not in host/, for the reason host_q32/itsolv_q32.cpp does: the handlers
 // call the mixed-precision C ABI, which the CPU emulation that host/ is also linked against does not have.
 #include "../host/rc_solver.h"
 #include "itsolv_hbm/hbm_handlers_f32.h"
@@ -15,6 +15,23 @@ std::unique_ptr<RcSolver> make_rc_davidson_q32(const std::string& options, size_
   solver->set_n_roots(nroot);
   if (auto* d = dynamic_cast<it::LinearEigensystemDavidson<Vec, VecF32, SparseP>*>(solver.get()))
     d->set_hermiticity(hermitian);
+  return std::make_unique<RcSolverOf<VecF32>>(std::move(solver), std::move(handlers), sizeof(float));
+}
+
+std::unique_ptr<RcSolver> make_rc_linear_equations_q32(const std::string& options, std::vector<Vec>& rhs, bool hermitian,
+                                                       double augmented_hessian, const double* refine_kappa) {
+  using molpro::linalg::hbm::VecF32;
+  using LinEq = it::LinearEquationsDavidson<Vec, VecF32, SparseP>;
+  auto handlers = molpro::linalg::hbm::make_handlers_q32();
+  auto solver = it::create_LinearEquations("Davidson", options, handlers);
+  auto* s = dynamic_cast<LinEq*>(solver.get());
+  if (!s) throw std::logic_error("Q_STORAGE=f32: LinearEquations is not the Davidson solver");
+  if (refine_kappa) s->set_refine(true, *refine_kappa);  // before the equations: their twins are kept from here on
+  s->set_hermiticity(hermitian);
+  s->set_n_roots(rhs.size());
+  s->add_equations(rhs);
+  if (augmented_hessian > 0) s->set_augmented_hessian(augmented_hessian);
+  if (refine_kappa) s->validate_refine();
   return std::make_unique<RcSolverOf<VecF32>>(std::move(solver), std::move(handlers), sizeof(float));
 }
 

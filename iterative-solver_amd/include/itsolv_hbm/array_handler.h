@@ -422,6 +422,15 @@ bool fused_residual_norms(H&, const std::vector<double>&, const RefX&, const Ref
   return false;
 }
 
+// Hook for LinearEquationsDavidson's construct_residual fused with update_errors' self-dots (reference
+// LinearEquationsDavidson.h:175-186: r_i -= b_i, r_i *= s_i with s_i = 1 / |b_i|; then
+// IterativeSolverTemplate.h:95-102): norms2[i] = <r_i, r_i> of the finished residuals; returns false,
+// touching nothing, when the handler has no such form.  Found by argument-dependent lookup.
+template <class H, class RefB, class RefR>
+bool fused_rhs_residual_norms(H&, const std::vector<double>&, const RefB&, const RefR&, std::vector<double>&) {
+  return false;
+}
+
 // Hook for solvers whose Q vectors are stored in a narrower format than their R vectors (the refined
 // mode of IterativeSolverTemplate): rounds each of `xx` in place to the values its copy into a Q vector
 // (`qr`, the Q x R handler's copy) would store, so that the copy made later is exact and an action

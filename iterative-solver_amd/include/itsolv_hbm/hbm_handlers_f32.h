@@ -414,6 +414,52 @@ inline bool fused_overlap_rows_mixed(array::ArrayHandler<Vec, VecF32>&, const it
   return true;
 }
 
+// The residuals of linear equations and their norms as one ssp_mx_rhs_residual_norms
+// (array::fused_rhs_residual_norms hook, LinearEquationsDavidson::construct_residual): r_i = s_i (r_i - b_i)
+// element for element the handler's axpy(-1) and scal, the norms update_errors' dots up to summation order, a
+// residual's pending scale applied as it is loaded.  The right-hand sides are the stored ones (VecF32) or, in the
+// refined mode, their f64 twins (Vec); both come through the R x Q handler of the q32 set, so a solver over
+// make_handlers() never gets here.  From fused_min_size(), as the other fused solver passes.
+namespace detail {
+template <class B>
+bool rhs_residual_norms(const std::vector<double>& s, const itsolv::CVecRef<B>& bb, ssp_dtype tb,
+                        const itsolv::VecRef<Vec>& yy, std::vector<double>& norms2) {
+  const size_t m = yy.size();
+  if (m == 0 || bb.size() < m || s.size() < m || yy.front().get().size() < fused_min_size()) return false;
+  const Vec& y0 = yy.front().get();
+  std::vector<const void*> bp;
+  for (size_t i = 0; i < m; ++i) {
+    const B& b = bb[i].get();
+    if (b.size() != y0.size() || b.offset() != y0.offset() || b.local_size() != y0.local_size())
+      throw array::util::ArrayHandlerError{"fused_rhs_residual_norms: arrays have different distributions"};
+    if constexpr (std::is_same_v<B, Vec>) {
+      if (b.scale() != 1.0) return false;  // (a right-hand side is a copy: it carries no pending scale)
+      bp.push_back(b.data_deferred());
+    } else {
+      bp.push_back(b.data());
+    }
+  }
+  std::vector<double> ys;
+  auto yp = rw_deferred_ptrs(yy, ys);
+  norms2.assign(m, 0.0);
+  check(ssp_mx_rhs_residual_norms(y0.ctx(), bp.data(), tb, s.data(), yp.data(), ys.data(), int(m), y0.local_size(),
+                                  norms2.data()),
+        "ssp_mx_rhs_residual_norms");
+  scales_applied(yy);
+  return true;
+}
+}  // namespace detail
+inline bool fused_rhs_residual_norms(array::ArrayHandler<Vec, VecF32>&, const std::vector<double>& s,
+                                     const itsolv::CVecRef<VecF32>& bb, const itsolv::VecRef<Vec>& yy,
+                                     std::vector<double>& norms2) {
+  return detail::rhs_residual_norms(s, bb, SSP_F32, yy, norms2);
+}
+inline bool fused_rhs_residual_norms(array::ArrayHandler<Vec, VecF32>&, const std::vector<double>& s,
+                                     const itsolv::CVecRef<Vec>& bb, const itsolv::VecRef<Vec>& yy,
+                                     std::vector<double>& norms2) {
+  return detail::rhs_residual_norms(s, bb, SSP_F64, yy, norms2);
+}
+
 // R vectors rounded in place to the values their narrowing copy into the Q space stores
 // (array::quantise_for_storage hook, the refined mode of solvers.h): one ssp_quantise_f32 for all of them, a
 // pending normalisation scale applied as the vector is loaded.  What qr().copy() makes of the result is exact.

@@ -251,13 +251,16 @@ void run_davidson(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Proble
 }
 
 // Runs LinearEquationsDavidson::solve on A x = b for the given right-hand sides and fills `out`;
-// residual_norms are |A x - b| / |b| recomputed by residual_norm(x, root).
+// residual_norms are |A x - b| / |b| recomputed by residual_norm(x, root).  refine_kappa, refine_stats: as
+// run_davidson's (the refined mode is set before the equations are added: it keeps their twins in R's format).
 template <class R, class Q, class P>
 void run_linear_equations(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Problem<R, P>& problem,
                           const std::function<R()>& make_vec, std::vector<R>& rhs,
                           const std::function<double(const R&, size_t)>& residual_norm, const itsolv_options& o,
-                          itsolv_result& out, const std::function<void(size_t, const R&)>& emit) {
+                          itsolv_result& out, const std::function<void(size_t, const R&)>& emit,
+                          const double* refine_kappa = nullptr, RefineStats* refine_stats = nullptr) {
   LinearEquationsDavidson<R, Q, P> solver(handlers);
+  if (refine_kappa) solver.set_refine(true, *refine_kappa);
   solver.add_equations(rhs);
   LinearEquationsDavidsonOptions opt;
   apply_options(o, opt);
@@ -284,6 +287,12 @@ void run_linear_equations(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, cons
   out.host_algebra_seconds = dense::AlgebraClock::seconds;
   out.host_algebra_calls = dense::AlgebraClock::calls;
   out.host_algebra_max_dim = int(dense::AlgebraClock::max_dim);
+  if (refine_stats) {
+    refine_stats->refined_actions = solver.refined_actions();
+    refine_stats->first_refined_iteration = solver.first_refined_iteration();
+    refine_stats->max_delta = 0;
+    for (double d : solver.refine_delta()) refine_stats->max_delta = std::max(refine_stats->max_delta, d);
+  }
   const auto& st = solver.statistics();
   out.iterations = st.iterations;
   out.r_creations = st.r_creations;

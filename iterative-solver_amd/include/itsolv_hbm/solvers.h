@@ -444,7 +444,8 @@ class IterativeSolverTemplate {
   //     of a batch in one call -- converged roots included, since the solver recomputes every root's residual
   //     in every iteration.  That is the price of actions stored in 4 bytes.
   // Scope: the hermitian LinearEigensystemDavidson, no max_size_qspace, reset_D or reset_D_max_Q_size, an
-  // empty D space (each is an error naming the option).  The refined residuals need the problem's action:
+  // empty D space (each is an error naming the option); and the hermitian LinearEquationsDavidson in the same
+  // scope, without the augmented Hessian and without set_refine_dspace (see its check_refine).  The refined residuals need the problem's action:
   // solve() provides it; a caller driving add_vector by hand gives it with set_refine_action, and rounds the
   // parameter vectors itself before it applies the action (step 1).  Without either, a needed refinement throws.
   void set_refine(bool on, double kappa = 8.0) {
@@ -661,8 +662,13 @@ class IterativeSolverTemplate {
 
   //! Throws unless this solver, as it is set up, supports the refined mode (set_refine).
   virtual void check_refine() const {
-    throw std::logic_error("refine: available for the hermitian LinearEigensystemDavidson only");
+    throw std::logic_error(
+        "refine: available for the hermitian LinearEigensystemDavidson and LinearEquationsDavidson only");
   }
+  //! What the bound delta of root i is multiplied by so that it is in the units of the solver's errors: 1 where
+  //! the error is the norm of the residual itself (exactly: the eigensolver's bits do not move), 1 / |b_i| where
+  //! the residual is relative to a right-hand side.
+  virtual double refine_delta_scale(int root) const { return 1.0; }
 
   // Step 3 of the refined mode (set_refine), after solution() has built the batch: the roots whose estimate
   // the bound no longer vouches for get r = H x - lambda x from the action of the solution itself (the P
@@ -688,6 +694,7 @@ class IterativeSolverTemplate {
       for (size_t j = 0; j < d.nQ; ++j) delta += std::abs(sol(size_t(roots[i]), d.oQ + j)) * norms.at(j);
       for (size_t j = 0; j < d.nD; ++j) delta += std::abs(sol(size_t(roots[i]), d.oD + j)) * dnorms.at(j);
       delta *= u;
+      delta *= refine_delta_scale(roots[i]);
       m_refine_delta[size_t(roots[i])] = delta;
       if (errors[i] <= std::max(m_refine_kappa * delta, m_convergence_threshold + delta)) {
         rroots.push_back(roots[i]);
@@ -1156,12 +1163,61 @@ class LinearEquationsDavidson : public DavidsonSolver<R, Q, P> {
   }
 
  protected:
-  // r_i = (A x_i - b_i) / |b_i| (reference :175-186)
+  // The refined mode (IterativeSolverTemplate::set_refine) for linear equations, in the scope of the eigensolver's
+  // without a D space; each limit is an error naming the option.  Beyond the shared steps it rests on two things:
+  // every right-hand side has a twin in R's format (XSpace::rhs_r; set_refine goes before add_equations), which
+  // the subspace rhs rows and the residuals read instead of the stored, rounded copy -- a residual against a
+  // rounded b could be no better than 2^-24 |b| -- and the bound delta_i is divided by |b_i|, as the errors are.
+  void check_refine() const override {
+    constexpr int unlimited = std::numeric_limits<int>::max();
+    if (!this->get_hermiticity()) throw std::runtime_error("refine: needs hermitian = 1 (hermiticity)");
+    if (this->m_refine_dspace)
+      throw std::runtime_error("refine: refine_dspace (Q_REFINE_DSPACE) is not available for LinearEquations");
+    if (this->get_max_size_qspace() != unlimited)
+      throw std::runtime_error("refine: max_size_qspace must be unlimited (a D space is not supported)");
+    if (this->get_reset_D() != unlimited) throw std::runtime_error("refine: reset_D must be off (a D space is not supported)");
+    if (this->get_reset_D_maxQ_size() != unlimited)
+      throw std::runtime_error("refine: reset_D_max_Q_size must be unlimited (a D space is not supported)");
+    if (const_cast<LinearEquationsDavidson*>(this)->get_augmented_hessian() != 0)
+      throw std::runtime_error("refine: augmented_hessian must be 0 (its residual is not A x - b)");
+    if (this->m_xspace->rhs_r().size() != this->m_xspace->rhs().size())
+      throw std::logic_error("refine: set_refine must be called before add_equations");
+  }
+  double refine_delta_scale(int root) const override {
+    const double b = this->m_xspace->rhs_norm().at(size_t(root));
+    return b != 0 ? 1 / b : 1.0;
+  }
+
+  // r_i = (A x_i - b_i) / |b_i| (reference :175-186); where the handler fuses the subtraction and the scaling
+  // with the residual norms (array::fused_rhs_residual_norms), the norms are kept for
+  // solve_and_generate_working_set's update_errors, as the eigensolver's are.  Refined mode: b_i is the twin in
+  // R's format, never the stored copy.
   void construct_residual(const std::vector<int>& roots, const CVecRef<R>& params, const VecRef<R>& actions) override {
     const auto& norm = this->m_xspace->rhs_norm();
+    const bool twins = this->m_refine;
+    const auto stored = rhs();
+    const auto exact = this->m_xspace->rhs_r();
+    std::vector<double> s(roots.size(), 1.0);
+    CVecRef<Q> bq;
+    CVecRef<R> br;
     for (size_t i = 0; i < roots.size(); ++i) {
       const auto ii = size_t(roots[i]);
-      this->m_handlers->rq().axpy(-1, rhs().at(ii), actions.at(i));
+      if (norm.at(ii) != 0) s[i] = 1 / norm[ii];
+      if (twins) br.push_back(exact.at(ii));
+      else bq.push_back(stored.at(ii));
+    }
+    const VecRef<R> res(actions.begin(), actions.begin() + long(roots.size()));
+    using array::fused_rhs_residual_norms;
+    const bool fused = twins ? fused_rhs_residual_norms(this->m_handlers->rq(), s, br, res, this->m_residual_norms2)
+                             : fused_rhs_residual_norms(this->m_handlers->rq(), s, bq, res, this->m_residual_norms2);
+    if (fused) {
+      this->m_handlers->rq().count_replaced(int(roots.size()), 0, 0);  // the axpys it replaced
+      return;
+    }
+    for (size_t i = 0; i < roots.size(); ++i) {
+      const auto ii = size_t(roots[i]);
+      if (twins) this->m_handlers->rr().axpy(-1, br[i], actions.at(i));
+      else this->m_handlers->rq().axpy(-1, bq[i], actions.at(i));
       if (norm.at(ii) != 0) this->m_handlers->rr().scal(1 / norm[ii], actions.at(i));
     }
   }

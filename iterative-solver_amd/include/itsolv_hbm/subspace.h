@@ -247,6 +247,11 @@ class XSpace {
   // (q_action_norms, Q order: newest first) for the solver's bound on the error of its residual.
   void set_refined(bool on) {
     if (on && m_dim.nQ + m_dim.nD != 0) throw std::logic_error("refine: must be set on an empty subspace");
+    // a right-hand side's twin in R's format cannot be rebuilt from its stored (rounded) copy
+    if (on && m_rhs_r.size() != m_rhs.size())
+      throw std::logic_error("refine: set_refine must be called before add_equations (the right-hand sides are "
+                             "already stored rounded; call set_refine(true) first, then add_equations)");
+    if (!on) m_rhs_r.clear();
     m_refined = on;
     m_refined_dspace = false;
     m_q_action_norms.clear();
@@ -296,9 +301,10 @@ class XSpace {
     using array::fused_overlap_rows_mixed;
     bool fused = false;
     if constexpr (!std::is_same_v<R, Q>)
-      fused = fused_overlap_rows_mixed(h.rq(), rows, std::vector<CVecRef<R>>{w, a}, std::vector<CVecRef<Q>>{qp, rhs()}, g);
+      fused = fused_overlap_rows_mixed(h.rq(), rows, std::vector<CVecRef<R>>{w, a, rhs_r()}, std::vector<CVecRef<Q>>{qp}, g);
     if (fused) {
-      const size_t cA = nd, cQ = 2 * nd, cR = cQ + d.nQ;
+      // columns [w, a, rhs twins | Q params]: the f64 columns first, then the stored ones
+      const size_t cA = nd, cR = 2 * nd, cQ = cR + d.nRHS;
       for (size_t i = 0; i < nd; ++i) {
         for (size_t j = 0; j <= i; ++j) S(d.oD + i, d.oD + j) = S(d.oD + j, d.oD + i) = g(i, j);
         for (size_t j = 0; j < nd; ++j) H(d.oD + i, d.oD + j) = g(i, cA + j);
@@ -321,7 +327,7 @@ class XSpace {
           S(d.oD + i, d.oQ + j) = S(d.oQ + j, d.oD + i) = sdq(i, j);
           H(d.oQ + j, d.oD + i) = H(d.oD + i, d.oQ + j) = hdq(i, j);
         }
-      if (d.nRHS) data[EqnData::rhs].slice({d.oD, 0}, {d.oD + d.nD, d.nRHS}) = util::overlap(w, rhs(), h.rq());
+      if (d.nRHS) data[EqnData::rhs].slice({d.oD, 0}, {d.oD + d.nD, d.nRHS}) = util::overlap(w, rhs_r(), h.rr());
       if constexpr (!std::is_same_v<R, Q>)  // (Q = R stores its actions exactly: no error to bound)
         for (size_t i = 0; i < nd; ++i) m_d_action_norms[i] = std::sqrt(std::abs(h.rr().dot(a[i].get(), a[i].get())));
     }
@@ -396,6 +402,9 @@ class XSpace {
 
   void add_rhs_equations(const CVecRef<R>& rhs_) {
     for (const auto& r : rhs_) m_rhs.emplace_back(m_handlers->qr().copy(r));
+    // refined mode: the twin in R's format, which every use of a right-hand side then reads instead
+    if (m_refined)
+      for (const auto& r : rhs_) m_rhs_r.emplace_back(m_handlers->rr().copy(r));
     for (const auto& r : rhs_) {
       const double d = std::abs(m_handlers->rr().dot(r, r));
       if (d == 0) throw std::runtime_error("RHS vector cannot be zero");
@@ -406,6 +415,9 @@ class XSpace {
   }
   CVecRef<Q> rhs() const { return cwrap(m_rhs); }
   const std::vector<double>& rhs_norm() const { return m_rhs_norm; }
+  //! The right-hand sides in R's format, kept in the refined mode only (set_refined); empty otherwise.  The
+  //! refined mode reads these wherever the other reads rhs(): the subspace rhs rows and the residuals.
+  CVecRef<R> rhs_r() const { return cwrap(m_rhs_r); }
 
   void eraseq(size_t i) {
     qspace.erase(i);
@@ -540,9 +552,10 @@ class XSpace {
         if (d.nD != 0 && !m_refined_dspace) throw std::runtime_error("refine: a D space is not supported");
         CVecRef<R> rows(params.begin(), params.end());
         rows.insert(rows.end(), actions.begin(), actions.end());
-        if (nn > 0 && fused_overlap_rows_mixed(h.rq(), rows, std::vector<CVecRef<R>>{params, actions},
-                                               std::vector<CVecRef<Q>>{qp, dp, rhs()}, g)) {
-          const size_t cA = nn, cQ = 2 * nn, cD = cQ + d.nQ, cR = cD + d.nD;
+        // Right-hand sides (linear equations) are f64 columns too: their twins in R's format (rhs_r).
+        if (nn > 0 && fused_overlap_rows_mixed(h.rq(), rows, std::vector<CVecRef<R>>{params, actions, rhs_r()},
+                                               std::vector<CVecRef<Q>>{qp, dp}, g)) {
+          const size_t cA = nn, cR = 2 * nn, cQ = cR + m_rhs.size(), cD = cQ + d.nQ;
           for (size_t i = 0; i < nn; ++i) {
             for (size_t j = 0; j <= i; ++j) qq[EqnData::S](i, j) = qq[EqnData::S](j, i) = g(i, j);
             for (size_t j = 0; j < nn; ++j) qq[EqnData::H](i, j) = g(i, cA + j);
@@ -566,7 +579,7 @@ class XSpace {
             qx[EqnData::S].slice({0, d.oD}, {nn, d.oD + d.nD}) = util::overlap(params, dp, h.rq());
             qx[EqnData::H].slice({0, d.oD}, {nn, d.oD + d.nD}) = util::overlap(actions, dp, h.rq());
           }
-          qq[EqnData::rhs] = util::overlap(params, rhs(), h.rq());
+          qq[EqnData::rhs] = util::overlap(params, rhs_r(), h.rr());
           for (size_t i = 0; i < nn; ++i)
             m_new_action_norms[i] = std::sqrt(std::abs(h.rr().dot(actions[i].get(), actions[i].get())));
         }
@@ -635,7 +648,9 @@ class XSpace {
   }
   void update_rhs_with_pspace() {
     data[EqnData::rhs].resize({m_dim.nP, m_dim.nRHS});
-    if (m_dim.nP && m_dim.nRHS) data[EqnData::rhs] = util::overlap(cparamsp(), rhs(), m_handlers->qp());
+    if (m_dim.nP && m_dim.nRHS)
+      data[EqnData::rhs] = m_refined ? util::overlap(cparamsp(), rhs_r(), m_handlers->rp())
+                                     : util::overlap(cparamsp(), rhs(), m_handlers->qp());
   }
   void remove_data(size_t i) {
     for (auto e : {EqnData::H, EqnData::S}) data[e].remove_row_col(i, i);
@@ -647,6 +662,7 @@ class XSpace {
   std::shared_ptr<Logger> m_logger;
   Dimensions m_dim;
   std::vector<Q> m_rhs;
+  std::vector<R> m_rhs_r;  // refined mode: every right-hand side in R's format (rhs_r)
   std::vector<double> m_rhs_norm;
   bool m_hermitian = false;
   bool m_action_dot_action = false;

@@ -631,6 +631,8 @@ class LinearEquations(IterativeSolver):
               options.encode())
         self._register()
         self._register_range(rb, re)
+        # solve() gives the refined mode (Q_STORAGE=f32,Q_REFINE=1) the problem's action, as LinearEigensystem's
+        self._refines = (_option(options, "Q_REFINE") or "0").upper() in ("1", "T", "TRUE")
 
 
 class Optimize(IterativeSolver):

@@ -26,11 +26,19 @@ EXPORTS = [
     "itsolv_davidson_dense_q32_refined", "itsolv_davidson_synth_q32_refined", "itsolv_q32_refine_stats",
     # the refined mode under a Q-space limit (a consistent D space), and what it spent on the D space
     "itsolv_davidson_dense_q32_refined_dspace", "itsolv_davidson_synth_q32_refined_dspace", "itsolv_q32_dspace_stats",
+    # linear equations on the synthetic H (f64), and dense / synthetic over the f32 Q space, plain and refined
+    "itsolv_linear_equations_synth",
+    "itsolv_linear_equations_dense_q32", "itsolv_linear_equations_synth_q32",
+    "itsolv_linear_equations_dense_q32_refined", "itsolv_linear_equations_synth_q32_refined",
 ]
+# Linear equations over the f32 Q space: absent from the CPU emulation of the library, as the sets below; a set
+# of their own (those stay what they were).
+OPTIONAL_LINEQ = frozenset(n for n in EXPORTS if n.startswith("itsolv_linear_equations_") and "_q32" in n)
 # Absent from the CPU emulation of the library (loaded through this binding by patching LIB_PATH).
-OPTIONAL = frozenset(n for n in EXPORTS if n.endswith("_q32"))
+OPTIONAL = frozenset(n for n in EXPORTS if n.endswith("_q32")) - OPTIONAL_LINEQ
 # The refined mode's entry points, optional in the same way; a set of their own: OPTIONAL stays the plain f32 Q space.
-OPTIONAL_REFINED = frozenset(n for n in EXPORTS if n.endswith("_q32_refined") or n == "itsolv_q32_refine_stats")
+OPTIONAL_REFINED = (frozenset(n for n in EXPORTS if n.endswith("_q32_refined") or n == "itsolv_q32_refine_stats")
+                    - OPTIONAL_LINEQ)
 # The refined mode's consistent D space, optional in the same way; again a set of its own.
 OPTIONAL_DSPACE = frozenset(n for n in EXPORTS if n.endswith("_q32_refined_dspace") or n == "itsolv_q32_dspace_stats")
 
@@ -171,9 +179,15 @@ def load_library():
             "itsolv_davidson_dense_q32_refined_dspace": (I, [P, PD, Z, PO, PF, PR, PD]),
             "itsolv_davidson_synth_q32_refined_dspace": (I, [P, Z, C.POINTER(Synth), PO, PF, PR, PD]),
             "itsolv_q32_dspace_stats": (I, [PI, PI]),
+            "itsolv_linear_equations_synth": (I, [P, Z, C.POINTER(Synth), I, U, PO, PR, PD]),
+            "itsolv_linear_equations_dense_q32": (I, [P, PD, Z, PD, I, PO, PR, PD]),
+            "itsolv_linear_equations_synth_q32": (I, [P, Z, C.POINTER(Synth), I, U, PO, PR, PD]),
+            "itsolv_linear_equations_dense_q32_refined": (I, [P, PD, Z, PD, I, PO, PF, PR, PD]),
+            "itsolv_linear_equations_synth_q32_refined": (I, [P, Z, C.POINTER(Synth), I, U, PO, PF, PR, PD]),
         }
+        optional = OPTIONAL | OPTIONAL_REFINED | OPTIONAL_DSPACE | OPTIONAL_LINEQ
         for name, (res, args) in sig.items():
-            if (name in OPTIONAL or name in OPTIONAL_REFINED or name in OPTIONAL_DSPACE) and not hasattr(L, name):
+            if name in optional and not hasattr(L, name):
                 continue
             f = getattr(L, name)
             f.restype = res
@@ -294,16 +308,42 @@ def diis_dense(ctx: sh.Context, h: np.ndarray, **opts):
     return r
 
 
-def linear_equations_dense(ctx: sh.Context, a: np.ndarray, rhs: np.ndarray, **opts):
-    """LinearEquationsDavidson on A x_r = b_r (rows of rhs); returns the result dict with "x"."""
+def linear_equations_dense(ctx: sh.Context, a: np.ndarray, rhs: np.ndarray, q32: bool = False, refine: bool = False,
+                           kappa: float | None = None, **opts):
+    """LinearEquationsDavidson on A x_r = b_r (rows of rhs); returns the result dict with "x".
+    q32: the Q space (and with it the right-hand sides) stored in f32: meaningful down to about 1e-6.
+    refine (with q32): the refined mode, which keeps an f64 twin of every right-hand side and reaches f64
+    thresholds at one more action per refined root and iteration; the result then has "refine"."""
+    fn = _entry("itsolv_linear_equations_dense", q32, refine)
     a = np.ascontiguousarray(a, dtype=np.float64)
     b = np.ascontiguousarray(np.atleast_2d(rhs), dtype=np.float64)
     n, nrhs = a.shape[0], b.shape[0]
     o = make_options(**opts)
-    r, x = _call(load_library().itsolv_linear_equations_dense,
-                 (ctx.handle, a.ctypes.data_as(C.POINTER(C.c_double)), n, b.ctypes.data_as(C.POINTER(C.c_double)),
-                  nrhs, C.byref(o)), n * nrhs)
+    r, x = _call(fn, (ctx.handle, a.ctypes.data_as(C.POINTER(C.c_double)), n, b.ctypes.data_as(C.POINTER(C.c_double)),
+                      nrhs, C.byref(o)) + _refine_args(refine, kappa), n * nrhs)
+    if refine:
+        r["refine"] = _refine_stats()
     r["x"] = x[:n * nrhs].reshape(nrhs, n)
+    return r
+
+
+def linear_equations_synth(ctx: sh.Context, n: int, rho: float, rank: int, seed: int, nrhs: int, rhs_seed: int,
+                           n_local: int | None = None, solutions: bool = True, *, diag_kind: int = DIAG_LINEAR,
+                           alpha: float = 0.0, q32: bool = False, refine: bool = False, kappa: float | None = None,
+                           **opts):
+    """LinearEquationsDavidson on the synthetic H (davidson_synthetic's; SPD for rho >= 0) with the right-hand
+    sides b_r = fill_random(seed=rhs_seed, vec=r); q32, refine, kappa: as linear_equations_dense's.  Returns the
+    result dict with "x" (nrhs x the local length) unless solutions is False."""
+    fn = _entry("itsolv_linear_equations_synth", q32, refine)
+    o = make_options(**opts)
+    nl = n if n_local is None else n_local
+    spec = Synth(rho, rank, seed, diag_kind, alpha, 1.0)
+    r, x = _call(fn, (ctx.handle, n, C.byref(spec), nrhs, rhs_seed, C.byref(o)) + _refine_args(refine, kappa),
+                 nrhs * nl if solutions else 0)
+    if refine:
+        r["refine"] = _refine_stats()
+    if solutions:
+        r["x"] = x[: nrhs * nl].reshape(nrhs, nl)
     return r
 
 

@@ -62,6 +62,8 @@ EXPORTS = [
     "ssp_rows_export_quantised",
     # new f32 vectors with their f64 twins (the consistent D space of the refined f32 Q space)
     "ssp_q32_combine_widen",
+    # residuals against right-hand sides and their norms in one pass (linear equations over an f32 Q space)
+    "ssp_mx_rhs_residual_norms",
 ]
 
 # The mixed-precision entry points are optional in a loaded library: the CPU emulation of the f64 C ABI
@@ -69,7 +71,10 @@ EXPORTS = [
 # SspError(SSP_ERR_UNSUPPORTED).
 # The entry points of the refined f32 Q space, optional in the same way and again a set of their own.
 OPTIONAL_REFINED = frozenset({"ssp_quantise_f32"})
-OPTIONAL = frozenset(n for n in EXPORTS if n.endswith("_f32") or n.startswith("ssp_mx_")) - OPTIONAL_REFINED
+# The fused residual pass of the linear equations over an f32 Q space, optional in the same way; a set of its own.
+OPTIONAL_LINEQ = frozenset({"ssp_mx_rhs_residual_norms"})
+OPTIONAL = (frozenset(n for n in EXPORTS if n.endswith("_f32") or n.startswith("ssp_mx_")) - OPTIONAL_REFINED
+            - OPTIONAL_LINEQ)
 # The fused passes over an f32 Q space are tolerated in the same way (absent from the emulation, a call
 # raises SspError(SSP_ERR_UNSUPPORTED)); they are a set of their own: OPTIONAL stays the storage layer.
 # The combine-and-widen pass of the refined mode's D space, optional in the same way; again a set of its own.
@@ -206,6 +211,7 @@ def _declare(lib):
         "ssp_mx_gemm_inner": (I, [P, P, I, PD, I, P, I, PD, I, Z, PD]),
         "ssp_mx_gemm_outer": (I, [P, PD, P, I, PD, I, P, I, I, Z, I]),
         "ssp_quantise_f32": (I, [P, P, PD, I, Z]),
+        "ssp_mx_rhs_residual_norms": (I, [P, P, I, PD, P, PD, I, Z, PD]),
         "ssp_q32_gemm_inner_cols": (I, [P, P, PD, I, P, C.POINTER(I), PD, I, Z, PD]),
         "ssp_q32_construct_solution": (I, [P, PD, PZ, PZ, PD, I, PD, P, I, P, I, Z, Z]),
         "ssp_q32_block_update": (I, [P, PD, PZ, PZ, PD, I, PD, P, I, P, PD, I, Z, Z]),
@@ -214,7 +220,7 @@ def _declare(lib):
         "ssp_rows_export": (I, [P, P, PD, I, P, Z, Z]),
         "ssp_rows_export_quantised": (I, [P, P, PD, I, I, P, Z, Z]),
     }
-    optional = OPTIONAL | OPTIONAL_Q32 | OPTIONAL_REFINED | OPTIONAL_ROWS | OPTIONAL_ROWS_Q | OPTIONAL_DSPACE
+    optional = OPTIONAL | OPTIONAL_Q32 | OPTIONAL_REFINED | OPTIONAL_ROWS | OPTIONAL_ROWS_Q | OPTIONAL_DSPACE | OPTIONAL_LINEQ
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -880,6 +886,23 @@ class Context:
         m = len(vectors)
         a = self._scales(xs, m)
         _check(f(self.handle, _ptrs(vectors), _dptr(a), m, vectors[0].n if m else 0))
+
+    def mx_rhs_residual_norms(self, bb: Sequence[DeviceVector], s: Sequence[float], yy: Sequence[DeviceVector],
+                              ys: Sequence[float] = None) -> np.ndarray:
+        """yy[j] = s[j] * (ys[j] * yy[j] - float64(bb[j])), then returns <yy[j], yy[j]>: the residuals of linear
+        equations against right-hand sides stored as float32 or float64, and their norms, in one pass."""
+        f = self._mx("ssp_mx_rhs_residual_norms")
+        m = len(yy)
+        if len(bb) != m or len(s) != m:
+            raise ValueError("mx_rhs_residual_norms: one right-hand side and one scale per residual")
+        if any(_code(v) != SSP_F64 for v in yy):
+            raise TypeError("mx_rhs_residual_norms: the residuals are float64 vectors")
+        ss = np.ascontiguousarray(s, dtype=np.float64)
+        sy = None if ys is None else np.ascontiguousarray(ys, dtype=np.float64)
+        out = np.zeros(max_(m))
+        _check(f(self.handle, _ptrs(bb), _same_dtype(bb) if m else SSP_F64, _dptr(ss), _ptrs(yy),
+                 None if sy is None else _dptr(sy), m, yy[0].n if m else 0, _dptr(out)))
+        return out[:m]
 
     def mx_axpy(self, alpha: float, x: DeviceVector, y: DeviceVector):
         _check(self._mx("ssp_mx_axpy")(self.handle, float(alpha), x.ptr, _code(x), y.ptr, _code(y), y.n))
