@@ -19,6 +19,8 @@ using molpro::linalg::hbm::SparseP;
 using molpro::linalg::hbm::Vec;
 using molpro::linalg::itsolv::CVecRef;
 using molpro::linalg::itsolv::Problem;
+using molpro::linalg::itsolv::RefineOptions;
+using molpro::linalg::itsolv::RefineStats;
 using molpro::linalg::itsolv::VecRef;
 namespace pr = molpro::linalg::itsolv::problems;
 
@@ -288,15 +290,25 @@ inline itsolv_options opts_or_default(const itsolv_options* o) {
   return o ? *o : d;
 }
 
+// The emit callback of the run_* drivers: the local part of every solution into `out` (null: nowhere), one
+// after the other.
+inline std::function<void(size_t, const Vec&)> emit_local(double* out) {
+  return [out](size_t r, const Vec& x) {
+    if (!out) return;
+    auto v = x.local_values();
+    std::memcpy(out + r * v.size(), v.data(), v.size() * sizeof(double));
+  };
+}
+
 // A x_r = b_r by LinearEquationsDavidson over the handler set `handlers` (Q = Vec, or the Q type of
 // host_q32/), for right-hand sides b already on the device.  residual_norms are |A x_r - b_r| / |b_r| recomputed
 // from the problem's action and b in f64; x_out (optional) takes the local part of every solution, one after
-// the other.  kappa, stats: the refined mode (pr::run_linear_equations).
+// the other.  refine, stats: the refined mode (pr::run_linear_equations).
 template <class Q, class PROB>
 void solve_linear_equations(const std::shared_ptr<Device>& dev, const PROB& problem, size_t n, std::vector<Vec>& b,
                             std::shared_ptr<molpro::linalg::itsolv::ArrayHandlers<Vec, Q, SparseP>> handlers,
-                            const itsolv_options& o, itsolv_result* out, double* x_out, const double* kappa = nullptr,
-                            pr::RefineStats* stats = nullptr) {
+                            const itsolv_options& o, itsolv_result* out, double* x_out,
+                            const RefineOptions* refine = nullptr, RefineStats* stats = nullptr) {
   std::memset(out, 0, sizeof(*out));
   pr::run_linear_equations<Vec, Q, SparseP>(
       std::move(handlers), problem, [&] { return zero_vec(dev, n); }, b,
@@ -310,20 +322,15 @@ void solve_linear_equations(const std::shared_ptr<Device>& dev, const PROB& prob
         return std::sqrt(std::abs(rr) / (bb > 0 ? bb : 1.0));
       },
       o, *out,
-      [&](size_t r, const Vec& x) {
-        if (!x_out) return;
-        auto v = x.local_values();
-        std::memcpy(x_out + r * v.size(), v.data(), v.size() * sizeof(double));
-      },
-      kappa, stats);
+      emit_local(x_out), refine, stats);
 }
 
 // The dense fixture (single rank): A row-major on the host, the right-hand sides the rows of rhs.
 template <class Q>
 void linear_equations_dense(ssp_ctx* ctx, const double* a, size_t n, const double* rhs, int nrhs,
                             std::shared_ptr<molpro::linalg::itsolv::ArrayHandlers<Vec, Q, SparseP>> handlers,
-                            const itsolv_options* opt, itsolv_result* out, double* x_out, const double* kappa = nullptr,
-                            pr::RefineStats* stats = nullptr) {
+                            const itsolv_options* opt, itsolv_result* out, double* x_out,
+                            const RefineOptions* refine = nullptr, RefineStats* stats = nullptr) {
   auto dev = borrow(ctx);
   DenseProblem problem(dev, a, n);
   std::vector<Vec> b;
@@ -332,7 +339,7 @@ void linear_equations_dense(ssp_ctx* ctx, const double* a, size_t n, const doubl
     check(ssp_upload(dev->ctx(), b.back().data_wo(), rhs + size_t(r) * n + b.back().offset(), b.back().local_size()),
           "ssp_upload");
   }
-  solve_linear_equations<Q>(dev, problem, n, b, std::move(handlers), opts_or_default(opt), out, x_out, kappa, stats);
+  solve_linear_equations<Q>(dev, problem, n, b, std::move(handlers), opts_or_default(opt), out, x_out, refine, stats);
 }
 
 // The synthetic H of sspx_synth (SPD for rho >= 0), sharded as the synthetic eigenproblem is; the right-hand
@@ -340,8 +347,8 @@ void linear_equations_dense(ssp_ctx* ctx, const double* a, size_t n, const doubl
 template <class Q>
 void linear_equations_synth(ssp_ctx* ctx, size_t n, const sspx_synth* spec, int nrhs, unsigned long long rhs_seed,
                             std::shared_ptr<molpro::linalg::itsolv::ArrayHandlers<Vec, Q, SparseP>> handlers,
-                            const itsolv_options* opt, itsolv_result* out, double* x_out, const double* kappa = nullptr,
-                            pr::RefineStats* stats = nullptr) {
+                            const itsolv_options* opt, itsolv_result* out, double* x_out,
+                            const RefineOptions* refine = nullptr, RefineStats* stats = nullptr) {
   auto dev = borrow(ctx);
   SyntheticProblem problem(dev, spec_of(n, spec));
   if (nrhs < 1 || nrhs > ITSOLV_MAX_ROOTS) throw std::invalid_argument("nrhs must be in [1, ITSOLV_MAX_ROOTS]");
@@ -352,8 +359,7 @@ void linear_equations_synth(ssp_ctx* ctx, size_t n, const sspx_synth* spec, int 
                            static_cast<unsigned long long>(r)),
           "sspx_fill_random");
   }
-  solve_linear_equations<Q>(dev, problem, n, b, std::move(handlers), opts_or_default(opt), out, x_out, kappa, stats);
+  solve_linear_equations<Q>(dev, problem, n, b, std::move(handlers), opts_or_default(opt), out, x_out, refine, stats);
 }
-
 
 }  // namespace itsolv_capi

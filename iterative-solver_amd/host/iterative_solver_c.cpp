@@ -266,7 +266,7 @@ struct RefineScratch {
   ~RefineScratch() { in.scratch_p = in.scratch_a = nullptr; }
 };
 
-// The solver's refine action (IterativeSolverTemplate::set_refine_action): the m selected solutions, compacted,
+// The solver's refine action (DavidsonSolver::set_refine_action): the m selected solutions, compacted,
 // into rows [0, m) of the call's parameters (pending scales applied), the caller's action on them, rows [0, m)
 // of its action array into the solver's vectors.
 void refine_action(Instance& in, const it::CVecRef<Vec>& x, const it::VecRef<Vec>& a) {
@@ -302,8 +302,10 @@ void refine_action(Instance& in, const it::CVecRef<Vec>& x, const it::VecRef<Vec
 }
 
 // Whether EndIteration returns its new parameter rows rounded to the Q storage format: the refined mode over
-// a Q space narrower than R (what solve() does before problem.action, solvers.h set_refine step 1).
-bool rounds_new_parameters(const Instance& in) { return in.solver->refine() && in.solver->q_bytes() < sizeof(double); }
+// a Q space narrower than R (what solve() does before problem.action, refine.h step 1).
+bool rounds_new_parameters(const Instance& in) {
+  return in.solver->refine_options().on && in.solver->q_bytes() < sizeof(double);
+}
 
 // solve() keeps the problem's diagonals in a Q vector; so does an instance whose Q space is narrower than R.
 // It matters: with actions stored rounded, the residual of a unit-vector guess is rounding noise (not an exact
@@ -458,7 +460,7 @@ void IterativeSolverLinearEigensystemInitialize(size_t nQ, size_t nroot, size_t*
     in.solver->set_convergence_threshold_value(thresh_value);
     // the refined mode's scope is checked here, not in the middle of a solve: hermitian = 0, MAX_SIZE_QSPACE,
     // RESET_D and RESET_D_MAX_Q_SIZE are errors naming the option (Q_REFINE_DSPACE=1 admits MAX_SIZE_QSPACE)
-    if (q.refine) in.solver->set_refine(true, q.kappa, q.dspace, q.dspace_slack);
+    if (q.refine) in.solver->set_refine(it::RefineOptions{true, q.kappa, q.dspace, q.dspace_slack});
     in.has_eigenvalues = true;
     setup(in, nQ, range_begin, range_end);
     push(std::move(in));
@@ -496,7 +498,7 @@ void IterativeSolverLinearEquationsInitialize(size_t n, size_t nroot, size_t* ra
       check(ssp_upload(in.dev->ctx(), b.back().data_wo(), rhs + r * n + in.offset, in.local), "ssp_upload");
     }
     if (q.f32) {  // the same construction over make_handlers_q32() (host_q32/rc_q32.cpp)
-      in.solver = make_lineq_q32_fn(options ? options : "", b, hermitian != 0, aughes, q.refine ? &q.kappa : nullptr);
+      in.solver = make_lineq_q32_fn(options ? options : "", b, hermitian != 0, aughes, it::RefineOptions{q.refine, q.kappa});
       in.solver->set_convergence_threshold(thresh);
       in.solver->set_convergence_threshold_value(thresh_value);
       in.solver->set_verbosity(verbosity_of(verbosity));
@@ -929,18 +931,18 @@ int IterativeSolverHbmSetRefineAction(itsolv_refine_action_fn fn, void* user) {
 
 int IterativeSolverHbmRefineStatistics(int* refined_actions, int* first_refined_iteration, double* max_delta) {
   if (instances.empty()) return 1;
-  const auto& s = *instances.back()->solver;
-  if (refined_actions) *refined_actions = s.refined_actions();
-  if (first_refined_iteration) *first_refined_iteration = s.first_refined_iteration();
-  if (max_delta) *max_delta = s.max_refine_delta();
+  const auto s = instances.back()->solver->refine_stats();
+  if (refined_actions) *refined_actions = s.refined_actions;
+  if (first_refined_iteration) *first_refined_iteration = s.first_refined_iteration;
+  if (max_delta) *max_delta = s.max_delta;
   return 0;
 }
 
 int IterativeSolverHbmRefineDspaceStats(int* rebuilds, int* actions) {
   if (instances.empty()) return 1;
-  const auto& s = *instances.back()->solver;
-  if (rebuilds) *rebuilds = s.dspace_rebuilds();
-  if (actions) *actions = s.dspace_actions();
+  const auto s = instances.back()->solver->refine_stats();
+  if (rebuilds) *rebuilds = s.dspace_rebuilds;
+  if (actions) *actions = s.dspace_actions;
   return 0;
 }
 

@@ -27,12 +27,7 @@ int itsolv_davidson_synth(ssp_ctx* ctx, size_t n, const sspx_synth* spec, const 
     pr::run_davidson<Vec, Vec, SparseP>(
         molpro::linalg::hbm::make_handlers(), problem, [&] { return zero_vec(dev, n); },
         [&](const Vec& x, double e) { return residual_norm(problem, dev, x, e); }, o, *out,
-        [&](size_t r, const Vec& x) {
-          if (!solutions_out) return;
-          auto v = x.local_values();
-          std::memcpy(solutions_out + r * v.size(), v.data(), v.size() * sizeof(double));
-        },
-        residual_norms_batch(problem, dev, n));
+        emit_local(solutions_out), residual_norms_batch(problem, dev, n));
   });
 }
 
@@ -46,11 +41,7 @@ int itsolv_davidson_dense(ssp_ctx* ctx, const double* h, size_t n, const itsolv_
     pr::run_davidson<Vec, Vec, SparseP>(
         molpro::linalg::hbm::make_handlers(), problem, [&] { return zero_vec(dev, n); },
         [&](const Vec& x, double e) { return residual_norm(problem, dev, x, e); }, o, *out,
-        [&](size_t r, const Vec& x) {
-          if (!solutions_out) return;
-          auto v = x.local_values();
-          std::memcpy(solutions_out + r * n, v.data(), n * sizeof(double));
-        });
+        emit_local(solutions_out));  // (a dense problem is on one rank: the local part is the whole)
   });
 }
 

@@ -49,18 +49,12 @@ class RcSolver {
   //! false for a solver without eigenvalues (nothing is written then)
   virtual bool eigenvalues(std::vector<double>& out) const = 0;
   virtual bool working_set_eigenvalues(std::vector<double>& out) const = 0;
-  // refined mode (itsolv_hbm/solvers.h set_refine)
-  //! also checks the mode's scope (errors name the option); dspace: with the consistent D space (set_refine_dspace),
-  //! dspace_slack >= 0: DavidsonSolver::set_refine_dspace_slack (negative: the solver's rule)
-  virtual void set_refine(bool on, double kappa, bool dspace = false, int dspace_slack = -1) = 0;
-  virtual bool refine() const = 0;
+  // refined mode (itsolv_hbm/refine.h)
+  //! also checks the mode's scope (errors name the option)
+  virtual void set_refine(const it::RefineOptions& o) = 0;
+  virtual it::RefineOptions refine_options() const = 0;
   virtual void set_refine_action(action_hook_type hook) = 0;
-  virtual int refined_actions() const = 0;
-  virtual int first_refined_iteration() const = 0;
-  virtual double max_refine_delta() const = 0;
-  virtual bool refine_dspace() const = 0;
-  virtual int dspace_rebuilds() const = 0;
-  virtual int dspace_actions() const = 0;
+  virtual it::RefineStats refine_stats() const = 0;
   //! bytes per stored Q element
   virtual size_t q_bytes() const = 0;
   //! rounds the vectors to the Q storage format in place (nothing for a Q space stored as R)
@@ -70,11 +64,15 @@ class RcSolver {
 template <class Q>
 class RcSolverOf final : public RcSolver {
   using Solver = it::IterativeSolverTemplate<Vec, Q, SparseP>;
+  using Davidson = it::DavidsonSolver<Vec, Q, SparseP>;
   using Handlers = std::shared_ptr<it::ArrayHandlers<Vec, Q, SparseP>>;
 
  public:
   RcSolverOf(std::unique_ptr<Solver> solver, Handlers handlers, size_t q_bytes = sizeof(double))
-      : m_s(std::move(solver)), m_h(std::move(handlers)), m_q_bytes(q_bytes) {}
+      : m_s(std::move(solver)),
+        m_davidson(dynamic_cast<Davidson*>(m_s.get())),
+        m_h(std::move(handlers)),
+        m_q_bytes(q_bytes) {}
 
   bool nonlinear() const override { return m_s->nonlinear(); }
   int add_vector(const it::VecRef<Vec>& p, const it::VecRef<Vec>& a) override { return m_s->add_vector(p, a); }
@@ -113,27 +111,25 @@ class RcSolverOf final : public RcSolver {
     out = m_s->working_set_eigenvalues();
     return true;
   }
-  void set_refine(bool on, double kappa, bool dspace = false, int dspace_slack = -1) override {
-    if (on && !dspace) m_s->validate_refine();
-    m_s->set_refine(on, kappa);
-    if (on && dspace) {  // the scope depends on the option: checked with it set
-      m_s->set_refine_dspace(true);
-      m_s->validate_refine();
-      if (auto* d = dynamic_cast<it::DavidsonSolver<Vec, Q, SparseP>*>(m_s.get())) d->set_refine_dspace_slack(dspace_slack);
+  void set_refine(const it::RefineOptions& o) override {
+    if (!m_davidson && o.on)
+      throw std::logic_error("refine: available for the hermitian LinearEigensystemDavidson and LinearEquationsDavidson only");
+    if (!m_davidson) return;
+    if (o.on && !o.dspace) m_davidson->validate_refine();
+    m_davidson->set_refine(o.on, o.kappa);
+    if (o.on && o.dspace) {  // the scope depends on the option: checked with it set
+      m_davidson->set_refine_dspace(true);
+      m_davidson->validate_refine();
+      m_davidson->set_refine_dspace_slack(o.dspace_slack);
     }
   }
-  bool refine_dspace() const override { return m_s->refine_dspace(); }
-  int dspace_rebuilds() const override { return m_s->dspace_rebuilds(); }
-  int dspace_actions() const override { return m_s->dspace_actions(); }
-  bool refine() const override { return m_s->refine(); }
-  void set_refine_action(action_hook_type hook) override { m_s->set_refine_action(std::move(hook)); }
-  int refined_actions() const override { return m_s->refined_actions(); }
-  int first_refined_iteration() const override { return m_s->first_refined_iteration(); }
-  double max_refine_delta() const override {
-    double d = 0;
-    for (double x : m_s->refine_delta()) d = std::max(d, x);
-    return d;
+  it::RefineOptions refine_options() const override {
+    return m_davidson ? m_davidson->refine_options() : it::RefineOptions{};
   }
+  void set_refine_action(action_hook_type hook) override {
+    if (m_davidson) m_davidson->set_refine_action(std::move(hook));
+  }
+  it::RefineStats refine_stats() const override { return m_davidson ? m_davidson->refine_stats() : it::RefineStats{}; }
   size_t q_bytes() const override { return m_q_bytes; }
   void quantise(const it::VecRef<Vec>& xx) override {
     using molpro::linalg::array::quantise_for_storage;
@@ -144,6 +140,7 @@ class RcSolverOf final : public RcSolver {
 
  private:
   std::unique_ptr<Solver> m_s;
+  Davidson* m_davidson;  // m_s where it is one, else null
   Handlers m_h;
   size_t m_q_bytes;
 };
@@ -153,11 +150,11 @@ class RcSolverOf final : public RcSolver {
 std::unique_ptr<RcSolver> make_rc_davidson_q32(const std::string& options, size_t nroot, bool hermitian)
     __attribute__((weak));
 // LinearEquations "Davidson" over the same handlers, for the right-hand sides rhs (R vectors), set up as
-// IterativeSolverLinearEquationsInitialize sets up the f64 solver.  refine_kappa: null for the plain f32 Q space;
-// else the refined mode with that kappa, set before the equations are added (it keeps their twins in R's
-// format) and its scope checked once everything is set (errors name the option).  Weak: null without host_q32/.
+// IterativeSolverLinearEquationsInitialize sets up the f64 solver.  refine.on: the refined mode, set before the
+// equations are added (it keeps their twins in R's format) and its scope checked once everything is set (errors
+// name the option); off: the plain f32 Q space.  Weak: null without host_q32/.
 std::unique_ptr<RcSolver> make_rc_linear_equations_q32(const std::string& options, std::vector<Vec>& rhs, bool hermitian,
-                                                       double augmented_hessian, const double* refine_kappa)
+                                                       double augmented_hessian, const it::RefineOptions& refine)
     __attribute__((weak));
 
 }  // namespace itsolv_rc

@@ -19,19 +19,19 @@ std::unique_ptr<RcSolver> make_rc_davidson_q32(const std::string& options, size_
 }
 
 std::unique_ptr<RcSolver> make_rc_linear_equations_q32(const std::string& options, std::vector<Vec>& rhs, bool hermitian,
-                                                       double augmented_hessian, const double* refine_kappa) {
+                                                       double augmented_hessian, const it::RefineOptions& refine) {
   using molpro::linalg::hbm::VecF32;
   using LinEq = it::LinearEquationsDavidson<Vec, VecF32, SparseP>;
   auto handlers = molpro::linalg::hbm::make_handlers_q32();
   auto solver = it::create_LinearEquations("Davidson", options, handlers);
   auto* s = dynamic_cast<LinEq*>(solver.get());
   if (!s) throw std::logic_error("Q_STORAGE=f32: LinearEquations is not the Davidson solver");
-  if (refine_kappa) s->set_refine(true, *refine_kappa);  // before the equations: their twins are kept from here on
+  if (refine.on) s->set_refine(true, refine.kappa);  // before the equations: their twins are kept from here on
   s->set_hermiticity(hermitian);
   s->set_n_roots(rhs.size());
   s->add_equations(rhs);
   if (augmented_hessian > 0) s->set_augmented_hessian(augmented_hessian);
-  if (refine_kappa) s->validate_refine();
+  if (refine.on) s->validate_refine();
   return std::make_unique<RcSolverOf<VecF32>>(std::move(solver), std::move(handlers), sizeof(float));
 }
 

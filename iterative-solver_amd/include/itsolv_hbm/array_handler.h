@@ -432,7 +432,7 @@ bool fused_rhs_residual_norms(H&, const std::vector<double>&, const RefB&, const
 }
 
 // Hook for solvers whose Q vectors are stored in a narrower format than their R vectors (the refined
-// mode of IterativeSolverTemplate): rounds each of `xx` in place to the values its copy into a Q vector
+// mode of DavidsonSolver, refine.h): rounds each of `xx` in place to the values its copy into a Q vector
 // (`qr`, the Q x R handler's copy) would store, so that the copy made later is exact and an action
 // computed in between belongs to the stored vector.  Returns false, touching nothing, when R and Q
 // store the same format.  Found by argument-dependent lookup.

@@ -159,29 +159,41 @@ void extract_solution_batches(Solver& solver, std::vector<R>& params, std::vecto
   }
 }
 
-// What a solve in the refined mode (solvers.h set_refine) spent: actions on refined residuals, the iteration
-// (from 1; 0: none) of the first, and the largest of the roots' last error bounds delta.
-struct RefineStats {
-  int refined_actions = 0;
-  int first_refined_iteration = 0;
-  double max_delta = 0;
-  // with the consistent D space (solvers.h set_refine_dspace): its rebuilds and the actions spent on them
-  int dspace_rebuilds = 0;
-  int dspace_actions = 0;
+// The clock, the algebra clock and the solver's statistics of a finished solve() into `out`.
+struct SolveClock {
+  SolveClock() {
+    dense::AlgebraClock::reset();
+    t0 = std::chrono::steady_clock::now();
+  }
+  template <class S>
+  void finish(const S& solver, itsolv_result& out) const {
+    out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    out.host_algebra_seconds = dense::AlgebraClock::seconds;
+    out.host_algebra_calls = dense::AlgebraClock::calls;
+    out.host_algebra_max_dim = int(dense::AlgebraClock::max_dim);
+    const auto& st = solver.statistics();
+    out.iterations = st.iterations;
+    out.r_creations = st.r_creations;
+    out.q_creations = st.q_creations;
+    out.redundant_params = st.redundant_params;
+    out.null_params = st.null_params;
+  }
+  std::chrono::steady_clock::time_point t0;
 };
 
-// refine_kappa: null for the plain solve; else the refined mode with that kappa (<= 0: the default), and
-// refine_stats (optional) filled after the solve.  refine_dspace: the refined mode's consistent D space
-// (set_refine_dspace), which admits max_size_qspace.
+// refine: null (or off) for the plain solve; else the refined mode of refine.h with these options, and stats
+// (optional) filled after the solve.
 template <class R, class Q, class P>
 void run_davidson(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Problem<R, P>& problem,
                   const std::function<R()>& make_vec, const std::function<double(const R&, double)>& residual_norm,
                   const itsolv_options& o, itsolv_result& out, const std::function<void(size_t, const R&)>& emit,
-                  const ResidualNormsBatch<R>& residual_norms_batch = {}, const double* refine_kappa = nullptr,
-                  RefineStats* refine_stats = nullptr, bool refine_dspace = false) {
+                  const ResidualNormsBatch<R>& residual_norms_batch = {}, const RefineOptions* refine = nullptr,
+                  RefineStats* stats = nullptr) {
   LinearEigensystemDavidson<R, Q, P> solver(handlers);
-  if (refine_kappa) solver.set_refine(true, *refine_kappa);
-  if (refine_dspace) solver.set_refine_dspace(true);
+  if (refine && refine->on) {
+    solver.set_refine(true, refine->kappa);
+    if (refine->dspace) solver.set_refine_dspace(true);
+  }
   LinearEigensystemDavidsonOptions opt;
   apply_options(o, opt);
   if (o.max_size_qspace > 0) opt.max_size_qspace = o.max_size_qspace;
@@ -198,27 +210,10 @@ void run_davidson(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Proble
   }
   out.n_eig_trace = 0;
   solver.iteration_hook = [&] { record_trace(solver, solver.eigenvalues(), out); };
-  dense::AlgebraClock::reset();
-  const auto t0 = std::chrono::steady_clock::now();
+  const SolveClock clock;
   out.converged = solver.solve(params, actions, problem, o.generate_initial_guess != 0);
-  out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  out.host_algebra_seconds = dense::AlgebraClock::seconds;
-  out.host_algebra_calls = dense::AlgebraClock::calls;
-  out.host_algebra_max_dim = int(dense::AlgebraClock::max_dim);
-  if (refine_stats) {
-    refine_stats->refined_actions = solver.refined_actions();
-    refine_stats->first_refined_iteration = solver.first_refined_iteration();
-    refine_stats->max_delta = 0;
-    for (double d : solver.refine_delta()) refine_stats->max_delta = std::max(refine_stats->max_delta, d);
-    refine_stats->dspace_rebuilds = solver.dspace_rebuilds();
-    refine_stats->dspace_actions = solver.dspace_actions();
-  }
-  const auto& st = solver.statistics();
-  out.iterations = st.iterations;
-  out.r_creations = st.r_creations;
-  out.q_creations = st.q_creations;
-  out.redundant_params = st.redundant_params;
-  out.null_params = st.null_params;
+  clock.finish(solver, out);
+  if (stats) *stats = solver.refine_stats();
   const auto ev = solver.eigenvalues();
   out.nroots = int(std::min<size_t>(ev.size(), ITSOLV_MAX_ROOTS));
   for (int i = 0; i < out.nroots; ++i) {
@@ -251,16 +246,16 @@ void run_davidson(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Proble
 }
 
 // Runs LinearEquationsDavidson::solve on A x = b for the given right-hand sides and fills `out`;
-// residual_norms are |A x - b| / |b| recomputed by residual_norm(x, root).  refine_kappa, refine_stats: as
+// residual_norms are |A x - b| / |b| recomputed by residual_norm(x, root).  refine, stats: as
 // run_davidson's (the refined mode is set before the equations are added: it keeps their twins in R's format).
 template <class R, class Q, class P>
 void run_linear_equations(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Problem<R, P>& problem,
                           const std::function<R()>& make_vec, std::vector<R>& rhs,
                           const std::function<double(const R&, size_t)>& residual_norm, const itsolv_options& o,
                           itsolv_result& out, const std::function<void(size_t, const R&)>& emit,
-                          const double* refine_kappa = nullptr, RefineStats* refine_stats = nullptr) {
+                          const RefineOptions* refine = nullptr, RefineStats* stats = nullptr) {
   LinearEquationsDavidson<R, Q, P> solver(handlers);
-  if (refine_kappa) solver.set_refine(true, *refine_kappa);
+  if (refine && refine->on) solver.set_refine(true, refine->kappa);
   solver.add_equations(rhs);
   LinearEquationsDavidsonOptions opt;
   apply_options(o, opt);
@@ -280,25 +275,10 @@ void run_linear_equations(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, cons
   }
   out.n_eig_trace = 0;
   solver.iteration_hook = [&] { record_trace(solver, std::vector<double>{}, out); };
-  dense::AlgebraClock::reset();
-  const auto t0 = std::chrono::steady_clock::now();
+  const SolveClock clock;
   out.converged = solver.solve(params, actions, problem, o.generate_initial_guess != 0);
-  out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  out.host_algebra_seconds = dense::AlgebraClock::seconds;
-  out.host_algebra_calls = dense::AlgebraClock::calls;
-  out.host_algebra_max_dim = int(dense::AlgebraClock::max_dim);
-  if (refine_stats) {
-    refine_stats->refined_actions = solver.refined_actions();
-    refine_stats->first_refined_iteration = solver.first_refined_iteration();
-    refine_stats->max_delta = 0;
-    for (double d : solver.refine_delta()) refine_stats->max_delta = std::max(refine_stats->max_delta, d);
-  }
-  const auto& st = solver.statistics();
-  out.iterations = st.iterations;
-  out.r_creations = st.r_creations;
-  out.q_creations = st.q_creations;
-  out.redundant_params = st.redundant_params;
-  out.null_params = st.null_params;
+  clock.finish(solver, out);
+  if (stats) *stats = solver.refine_stats();
   out.nroots = int(std::min<size_t>(nwork, ITSOLV_MAX_ROOTS));
   for (int i = 0; i < out.nroots; ++i) {
     out.eigenvalues[i] = 0;
@@ -336,19 +316,9 @@ void run_optimize(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Proble
   init(x);
   out.n_eig_trace = 0;
   solver->iteration_hook = [&] { record_trace(*solver, std::vector<double>{solver->value()}, out); };
-  dense::AlgebraClock::reset();
-  const auto t0 = std::chrono::steady_clock::now();
+  const SolveClock clock;
   out.converged = solver->solve(x, g, problem);
-  out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  out.host_algebra_seconds = dense::AlgebraClock::seconds;
-  out.host_algebra_calls = dense::AlgebraClock::calls;
-  out.host_algebra_max_dim = int(dense::AlgebraClock::max_dim);
-  const auto& st = solver->statistics();
-  out.iterations = st.iterations;
-  out.r_creations = st.r_creations;
-  out.q_creations = st.q_creations;
-  out.redundant_params = st.redundant_params;
-  out.null_params = st.null_params;
+  clock.finish(*solver, out);
   out.nroots = 1;
   out.errors[0] = solver->errors().empty() ? 0.0 : solver->errors().front();
   out.eigenvalues[0] = solver->value();
@@ -374,19 +344,9 @@ void run_diis(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Problem<R,
   init(x);
   out.n_eig_trace = 0;
   solver.iteration_hook = [&] { record_trace(solver, std::vector<double>{}, out); };
-  dense::AlgebraClock::reset();
-  const auto t0 = std::chrono::steady_clock::now();
+  const SolveClock clock;
   out.converged = solver.solve(x, g, problem);
-  out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  out.host_algebra_seconds = dense::AlgebraClock::seconds;
-  out.host_algebra_calls = dense::AlgebraClock::calls;
-  out.host_algebra_max_dim = int(dense::AlgebraClock::max_dim);
-  const auto& st = solver.statistics();
-  out.iterations = st.iterations;
-  out.r_creations = st.r_creations;
-  out.q_creations = st.q_creations;
-  out.redundant_params = st.redundant_params;
-  out.null_params = st.null_params;
+  clock.finish(solver, out);
   out.nroots = 1;
   out.errors[0] = solver.errors().empty() ? 0.0 : solver.errors().front();
   out.eigenvalues[0] = 0;

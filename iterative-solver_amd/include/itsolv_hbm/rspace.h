@@ -334,7 +334,7 @@ R scratch_like(array::ArrayHandler<R, R>& h, const R& x) {
   else return h.copy(x);
 }
 
-// The parameters of the new D space in the refined mode (solvers.h set_refine_dspace), for a Q space stored
+// The parameters of the new D space in the refined mode (refine.h, DavidsonSolver::set_refine_dspace), for a Q space stored
 // narrower than R: the coefficients of construct_dspace, then one pass over the source PARAMETERS (the Q vectors
 // being deleted, then the old D) that stores each new vector rounded once and, in twin[i], that stored value in
 // R's format -- the vector whose action the solver takes next, so that the D space's actions belong to its

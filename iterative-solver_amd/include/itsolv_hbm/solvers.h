@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "interpolate.h"
+#include "refine.h"
 #include "rspace.h"
 
 namespace molpro::linalg::itsolv {
@@ -430,67 +431,6 @@ class IterativeSolverTemplate {
   std::shared_ptr<Logger> logger() const { return m_logger; }
   subspace::XSpace<R, Q, P>& xspace() { return *m_xspace; }
 
-  // Refined mode, for a Q space stored in a narrower format than R (extension; off by default, and then
-  // every path is as it was).  Three things change, all in solve():
-  //  1. each new R parameter vector is rounded to the Q storage format (array::quantise_for_storage) before
-  //     problem.action sees it, so its copy into the Q space is exact and a_j = H q_j to the precision of R;
-  //  2. the new rows of H come from the stored Q parameters and the new actions in R's precision
-  //     (subspace.h XSpace::set_refined), so S and H are the exact projection onto span{q_j};
-  //  3. only the stored actions then carry error: for root i, |r_est - r_true| <= delta_i =
-  //     u sum_j |c_ji| |a_j| with u the unit roundoff of the storage (2^-24) and |a_j| kept on the host.
-  //     A root with est_i <= max(kappa delta_i, threshold + delta_i) -- its estimate is no longer accurate to
-  //     1 / kappa, or it could be declared converged on an unverified estimate -- gets its residual from
-  //     the action of its solution instead: one more action per such root and iteration, all refined roots
-  //     of a batch in one call -- converged roots included, since the solver recomputes every root's residual
-  //     in every iteration.  That is the price of actions stored in 4 bytes.
-  // Scope: the hermitian LinearEigensystemDavidson, no max_size_qspace, reset_D or reset_D_max_Q_size, an
-  // empty D space (each is an error naming the option); and the hermitian LinearEquationsDavidson in the same
-  // scope, without the augmented Hessian and without set_refine_dspace (see its check_refine).  The refined residuals need the problem's action:
-  // solve() provides it; a caller driving add_vector by hand gives it with set_refine_action, and rounds the
-  // parameter vectors itself before it applies the action (step 1).  Without either, a needed refinement throws.
-  void set_refine(bool on, double kappa = 8.0) {
-    m_xspace->set_refined(on);
-    m_refine = on;
-    m_refine_kappa = kappa > 0 ? kappa : 8.0;
-    m_refined_actions = 0;
-    m_first_refined_iteration = 0;
-    m_refine_delta.clear();
-    m_refine_dspace = false;
-    m_dspace_rebuilds = m_dspace_actions = 0;
-  }
-  bool refine() const { return m_refine; }
-  // The refined mode under a Q-space limit (opt-in; call after set_refine(true)).  With it, check_refine accepts
-  // a finite max_size_qspace, and whenever the limit deletes Q vectors the D space is rebuilt consistently:
-  // the new D parameters are written by one pass over the deleted Q and old D PARAMETERS, rounded once, with
-  // their values in R's format beside them (rspace.h construct_dspace_refined); the D actions are true actions
-  // of exactly those vectors, one call of the action hook for all of them; and the D blocks of S and H come
-  // from these in R's precision (subspace.h update_dspace_refined).  The bound delta_i then has the D terms
-  // u sum_d |c_di| |a_d|.  Cost: nD <= n_roots actions per rebuild, a rebuild in every iteration in which the
-  // limit deletes something -- which propose_rspace makes rarer by cutting the Q space below the limit
-  // (DavidsonSolver::set_refine_dspace_slack).  reset_D / reset_D_max_Q_size stay outside the scope.
-  void set_refine_dspace(bool on) {
-    if (on && !m_refine) throw std::logic_error("refine_dspace: needs the refined mode (set_refine) first");
-    m_xspace->set_refined_dspace(on);
-    m_refine_dspace = on;
-    m_dspace_rebuilds = m_dspace_actions = 0;
-  }
-  bool refine_dspace() const { return m_refine_dspace; }
-  //! rebuilds of the D space under the Q-space limit (in either mode), and the actions the refined mode spent
-  //! on them (not in refined_actions())
-  int dspace_rebuilds() const { return m_dspace_rebuilds; }
-  int dspace_actions() const { return m_dspace_actions; }
-  double refine_kappa() const { return m_refine_kappa; }
-  //! actions spent on refined residuals; the iteration (from 1) of the first; the last delta of each root
-  int refined_actions() const { return m_refined_actions; }
-  int first_refined_iteration() const { return m_first_refined_iteration; }
-  const std::vector<double>& refine_delta() const { return m_refine_delta; }
-  //! The action the refined residuals are formed with: actions[k] = H parameters[k].  It stays until it is
-  //! replaced or cleared (an empty hook); solve() uses the problem's action for its duration and restores it.
-  using action_hook_type = std::function<void(const CVecRef<R>&, const VecRef<R>&)>;
-  void set_refine_action(action_hook_type hook) { m_action_hook = std::move(hook); }
-  //! Throws unless this solver, as it is set up now, supports the refined mode (what set_refine's scope names).
-  void validate_refine() const { check_refine(); }
-
   //! The current settings (reference IterativeSolverTemplate.h:262-267; derived solvers add theirs).
   virtual std::shared_ptr<Options> get_options() const {
     auto o = std::make_shared<Options>();
@@ -513,16 +453,7 @@ class IterativeSolverTemplate {
              bool generate_initial_guess = false) {
     if (parameters.empty()) throw std::runtime_error("Empty container passed to IterativeSolver::solve()");
     if (parameters.size() != actions.size()) throw std::runtime_error("Inconsistent container sizes in IterativeSolver::solve()");
-    // refined mode: the solver reaches the problem's action for the refined residuals while solve() runs
-    struct HookScope {
-      action_hook_type& hook;
-      action_hook_type callers;  // set_refine_action's: restored on every way out
-      ~HookScope() { hook = std::move(callers); }
-    } hook_scope{m_action_hook, m_action_hook};
-    if (m_refine) {
-      check_refine();
-      m_action_hook = [&problem](const CVecRef<R>& x, const VecRef<R>& a) { problem.action(x, a); };
-    }
+    const auto scope = solve_scope(problem);
     const bool use_diagonals = problem.diagonals(actions.at(0));
     std::unique_ptr<Q> diagonals;
     if (use_diagonals) diagonals = std::make_unique<Q>(m_handlers->qr().copy(actions.at(0)));
@@ -553,10 +484,7 @@ class IterativeSolverTemplate {
         const auto value = problem.residual(parameters.front(), actions.front());
         nwork = add_vector(parameters.front().get(), actions.front().get(), value);
       } else if (iter > 0 || pspace.empty()) {
-        if (m_refine) {  // the action must belong to the vector the Q space will hold
-          using array::quantise_for_storage;
-          quantise_for_storage(m_handlers->qr(), wrap(parameters.begin(), parameters.begin() + nwork));
-        }
+        before_action(wrap(parameters.begin(), parameters.begin() + nwork));
         problem.action(cwrap(parameters.begin(), parameters.begin() + nwork), wrap(actions.begin(), actions.begin() + nwork));
         nwork = add_vector(parameters, actions);
       }
@@ -611,6 +539,15 @@ class IterativeSolverTemplate {
   }
 
   virtual void set_value_errors() {}
+  // Three places where a derived solver may step in; each does nothing here.
+  //! solve() is entered: what is returned is let go when solve() is left, on every way out
+  virtual std::shared_ptr<void> solve_scope(const Problem<R, P>& problem) { return nullptr; }
+  //! solve() is about to call problem.action on these new parameters
+  virtual void before_action(const VecRef<R>& parameters) {}
+  //! solve_and_generate_working_set has the errors of a batch of roots, whose solutions and residuals are in
+  //! parameters and action
+  virtual void after_errors(const std::vector<int>& roots, const VecRef<R>& parameters, const VecRef<R>& action,
+                            std::vector<double>& errors) {}
   virtual void construct_residual(const std::vector<int>& roots, const CVecRef<R>& params, const VecRef<R>& actions) = 0;
 
   // reference IterativeSolverTemplate.h:518-563
@@ -632,7 +569,7 @@ class IterativeSolverTemplate {
         detail::update_errors(errors, cwrap(action), m_handlers->rr());
       }
       m_residual_norms2.clear();
-      if (m_refine) refine_residuals(roots, parameters, action, errors);
+      after_errors(roots, parameters, action, errors);
       if (batches.size() > 1) {
         for (size_t i = 0; i < roots.size(); ++i)
           temp.emplace_back(m_handlers->qr().copy(parameters[i]), m_handlers->qr().copy(action[i]));
@@ -660,72 +597,6 @@ class IterativeSolverTemplate {
     return m_working_set.size();
   }
 
-  //! Throws unless this solver, as it is set up, supports the refined mode (set_refine).
-  virtual void check_refine() const {
-    throw std::logic_error(
-        "refine: available for the hermitian LinearEigensystemDavidson and LinearEquationsDavidson only");
-  }
-  //! What the bound delta of root i is multiplied by so that it is in the units of the solver's errors: 1 where
-  //! the error is the norm of the residual itself (exactly: the eigensolver's bits do not move), 1 / |b_i| where
-  //! the residual is relative to a right-hand side.
-  virtual double refine_delta_scale(int root) const { return 1.0; }
-
-  // Step 3 of the refined mode (set_refine), after solution() has built the batch: the roots whose estimate
-  // the bound no longer vouches for get r = H x - lambda x from the action of the solution itself (the P
-  // space's part is inside H x: no apply_p), and their errors are recomputed.  The decision uses reduced
-  // quantities only (estimates, subspace coefficients, action norms), so every rank takes it alike.
-  void refine_residuals(const std::vector<int>& roots, const VecRef<R>& parameters, const VecRef<R>& action,
-                        std::vector<double>& errors) {
-    const auto& d = m_xspace->dimensions();
-    if (d.nQ + (m_refine_dspace ? d.nD : 0) == 0) return;  // nothing is stored rounded yet
-    if (d.nD != 0 && !m_refine_dspace) throw std::runtime_error("refine: a D space is not supported");
-    require_action_hook();
-    check_refine();
-    const auto& norms = m_xspace->q_action_norms();
-    const auto& dnorms = m_xspace->d_action_norms();
-    const auto& sol = m_subspace_solver->solutions();
-    constexpr double u = 5.9604644775390625e-08;  // 2^-24, the unit roundoff of binary32
-    if (m_refine_delta.size() < sol.rows()) m_refine_delta.resize(sol.rows(), 0.0);
-    std::vector<int> rroots;
-    VecRef<R> rx, ra;
-    std::vector<size_t> slot;
-    for (size_t i = 0; i < roots.size(); ++i) {
-      double delta = 0;
-      for (size_t j = 0; j < d.nQ; ++j) delta += std::abs(sol(size_t(roots[i]), d.oQ + j)) * norms.at(j);
-      for (size_t j = 0; j < d.nD; ++j) delta += std::abs(sol(size_t(roots[i]), d.oD + j)) * dnorms.at(j);
-      delta *= u;
-      delta *= refine_delta_scale(roots[i]);
-      m_refine_delta[size_t(roots[i])] = delta;
-      if (errors[i] <= std::max(m_refine_kappa * delta, m_convergence_threshold + delta)) {
-        rroots.push_back(roots[i]);
-        rx.push_back(parameters[i]);
-        ra.push_back(action[i]);
-        slot.push_back(i);
-      }
-    }
-    if (rroots.empty()) return;
-    m_action_hook(cwrap(rx.begin(), rx.end()), ra);
-    m_refined_actions += int(rroots.size());
-    if (m_first_refined_iteration == 0) m_first_refined_iteration = m_stats->iterations + 1;
-    m_residual_norms2.clear();
-    construct_residual(rroots, cwrap(rx.begin(), rx.end()), ra);
-    std::vector<double> e(rroots.size(), 0);
-    if (m_residual_norms2.size() == rroots.size()) {
-      for (size_t i = 0; i < e.size(); ++i) e[i] = std::sqrt(std::abs(m_residual_norms2[i]));
-    } else {
-      detail::update_errors(e, cwrap(ra.begin(), ra.end()), m_handlers->rr());
-    }
-    m_residual_norms2.clear();
-    for (size_t i = 0; i < e.size(); ++i) errors[slot[i]] = e[i];
-  }
-
-  void require_action_hook() const {
-    if (!m_action_hook)
-      throw std::logic_error(
-          "refine: needs the problem's action, which only solve() provides (not add_vector by hand) unless "
-          "set_refine_action has given it (C API: IterativeSolverHbmSetRefineAction)");
-  }
-
   void check_roots(const std::vector<int>& roots, size_t nparams) const {
     if (roots.size() > nparams) throw std::runtime_error("asking for more roots than parameters");
     if (!roots.empty() && size_t(*std::max_element(roots.begin(), roots.end())) >= m_subspace_solver->solutions().rows())
@@ -750,16 +621,6 @@ class IterativeSolverTemplate {
   size_t m_max_p = 0;
   double m_p_threshold = std::numeric_limits<double>::max();
   bool m_end_iteration_needed = true;
-  // refined mode (set_refine)
-  bool m_refine = false;
-  double m_refine_kappa = 8.0;
-  action_hook_type m_action_hook{};  // set_refine_action's; problem.action while solve() runs
-  int m_refined_actions = 0;
-  int m_first_refined_iteration = 0;  // 0: none yet
-  std::vector<double> m_refine_delta;
-  bool m_refine_dspace = false;  // set_refine_dspace
-  int m_dspace_rebuilds = 0;
-  int m_dspace_actions = 0;
 };
 
 // ---- Davidson ----------------------------------------------------------------------------------
@@ -804,26 +665,37 @@ class DavidsonSolver : public IterativeSolverTemplate<R, Q, P> {
     m_max_size_qspace = n;
     if (m_resetter.get_max_Qsize() > m_max_size_qspace) m_resetter.set_max_Qsize(size_t(m_max_size_qspace));
   }
-  //! How far below max_size_qspace a rebuild of the refined mode's D space (set_refine_dspace) cuts the Q space.
-  //! 0 is the reference's schedule: delete just enough, so a rebuild in every iteration once the Q space is
-  //! full.  Unset (the default, or a negative n) it is a rule in whole working sets (less than one spaces
-  //! nothing): two per rebuild -- a rebuild every third iteration -- or one, whichever stays under a quarter of
-  //! the limit; none where the limit is that tight, because there the smaller Q space costs more iterations
-  //! than the rarer rounding saves.  The rule's constants were measured on one dense fixture
-  //! (profiles/r14/q32_refined_dspace.md); a caller who knows better sets the value.  A value is cut to leave
-  //! at least n_roots Q vectors.
-  void set_refine_dspace_slack(int n) {
-    if (n < 0)
-      m_refine_dspace_slack.reset();
-    else
-      m_refine_dspace_slack = n;
+  // ---- the refined mode of an f32 Q space (refine.h): this class is its home in the solver -----------------
+  using action_hook_type = typename Refinement<R>::action_hook_type;
+  //! The mode on or off, every counter and set_refine_dspace reset.  For linear equations: before add_equations.
+  void set_refine(bool on, double kappa = 8.0) {
+    this->m_xspace->set_refined(on);
+    m_refine.set(on, kappa);
   }
-  int refine_dspace_slack() const {
-    if (m_max_size_qspace == std::numeric_limits<int>::max()) return 0;
-    const size_t nr = this->n_roots(), quarter4 = size_t(m_max_size_qspace);  // 4 x a quarter of the limit
-    if (m_refine_dspace_slack) return std::min(*m_refine_dspace_slack, std::max(0, m_max_size_qspace - int(nr)));
-    return 4 * 2 * nr < quarter4 ? int(2 * nr) : 4 * nr < quarter4 ? int(nr) : 0;
+  //! The consistent D space, which admits max_size_qspace (after set_refine(true))
+  void set_refine_dspace(bool on) {
+    m_refine.set_dspace(on);  // throws where the mode is not on
+    this->m_xspace->set_refined_dspace(on);
   }
+  //! negative: the default rule (Refinement::dspace_slack)
+  void set_refine_dspace_slack(int n) { m_refine.options.dspace_slack = n < 0 ? -1 : n; }
+  //! The action the refined residuals are formed with: actions[k] = H parameters[k].  It stays until it is
+  //! replaced or cleared (an empty hook); solve() uses the problem's action for its duration and restores it.
+  void set_refine_action(action_hook_type hook) { m_refine.hook = std::move(hook); }
+  //! Throws unless this solver, as it is set up now, supports the refined mode (errors name the option).
+  void validate_refine() const { check_refine(); }
+  const RefineOptions& refine_options() const { return m_refine.options; }
+  bool refine() const { return m_refine.options.on; }
+  double refine_kappa() const { return m_refine.options.kappa; }
+  bool refine_dspace() const { return m_refine.options.dspace; }
+  int refine_dspace_slack() const { return m_refine.dspace_slack(this->n_roots(), m_max_size_qspace); }
+  RefineStats refine_stats() const { return m_refine.current_stats(); }
+  int refined_actions() const { return m_refine.stats.refined_actions; }
+  int first_refined_iteration() const { return m_refine.stats.first_refined_iteration; }
+  const std::vector<double>& refine_delta() const { return m_refine.delta; }
+  int dspace_rebuilds() const { return m_refine.stats.dspace_rebuilds; }
+  int dspace_actions() const { return m_refine.stats.dspace_actions; }
+
   void set_hermiticity(bool h) {
     m_hermiticity = h;
     this->m_xspace->set_hermiticity(h);
@@ -868,6 +740,89 @@ class DavidsonSolver : public IterativeSolverTemplate<R, Q, P> {
   std::optional<bool> block_gram_schmidt() const { return m_block_gram_schmidt; }
 
  protected:
+  // The refined mode's scope (refine.h): each limit is an error naming the option.  A leaf adds its own with
+  // check_refine_dspace (whether the consistent D space is to be had at all) and check_refine_more.
+  void check_refine() const {
+    constexpr int unlimited = std::numeric_limits<int>::max();
+    const bool dspace = m_refine.options.dspace;
+    if (!get_hermiticity()) throw std::runtime_error("refine: needs hermitian = 1 (hermiticity)");
+    if (dspace) check_refine_dspace();
+    if (get_max_size_qspace() != unlimited && !dspace)
+      throw std::runtime_error("refine: max_size_qspace must be unlimited (a D space is not supported)");
+    if (get_reset_D() != unlimited) throw std::runtime_error("refine: reset_D must be off (a D space is not supported)");
+    // (set_max_size_qspace lowers reset_D_max_Q_size to the limit with it: that implied value is no request
+    // for a reset, which reset_D alone turns on.  A caller's own reset_D_max_Q_size equal to the limit cannot be
+    // told from it and passes too; it has no effect while reset_D is refused above.)
+    const bool implied = dspace && get_reset_D_maxQ_size() == get_max_size_qspace();
+    if (get_reset_D_maxQ_size() != unlimited && !implied)
+      throw std::runtime_error("refine: reset_D_max_Q_size must be unlimited (a D space is not supported)");
+    check_refine_more();
+  }
+  virtual void check_refine_dspace() const {}
+  virtual void check_refine_more() const {}
+  //! What the bound delta of root i is multiplied by so that it is in the units of the solver's errors: 1 where
+  //! the error is the norm of the residual itself (exactly: the eigensolver's bits do not move), 1 / |b_i| where
+  //! the residual is relative to a right-hand side.
+  virtual double refine_delta_scale(int root) const { return 1.0; }
+
+  // solve() reaches the problem's action for the refined residuals while it runs; the scope is checked first
+  std::shared_ptr<void> solve_scope(const Problem<R, P>& problem) override {
+    if (!m_refine.options.on) return nullptr;
+    check_refine();
+    return std::make_shared<typename Refinement<R>::HookScope>(
+        m_refine.hook, [&problem](const CVecRef<R>& x, const VecRef<R>& a) { problem.action(x, a); });
+  }
+  // step 1: the action must belong to the vector the Q space will hold
+  void before_action(const VecRef<R>& parameters) override {
+    if (!m_refine.options.on) return;
+    using array::quantise_for_storage;
+    quantise_for_storage(this->m_handlers->qr(), parameters);
+  }
+  // Step 3, after solution() has built the batch: the roots whose estimate the bound no longer vouches for get
+  // r = H x - lambda x from the action of the solution itself (the P space's part is inside H x: no apply_p),
+  // and their errors are recomputed.  The decision uses reduced quantities only (estimates, subspace
+  // coefficients, action norms), so every rank takes it alike.
+  void after_errors(const std::vector<int>& roots, const VecRef<R>& parameters, const VecRef<R>& action,
+                    std::vector<double>& errors) override {
+    if (!m_refine.options.on) return;
+    const bool dspace = m_refine.options.dspace;
+    const auto& d = this->m_xspace->dimensions();
+    if (d.nQ + (dspace ? d.nD : 0) == 0) return;  // nothing is stored rounded yet
+    if (d.nD != 0 && !dspace) throw std::runtime_error("refine: a D space is not supported");
+    m_refine.require_hook();
+    check_refine();
+    const auto& sol = this->m_subspace_solver->solutions();
+    if (m_refine.delta.size() < sol.rows()) m_refine.delta.resize(sol.rows(), 0.0);
+    std::vector<int> rroots;
+    VecRef<R> rx, ra;
+    std::vector<size_t> slot;
+    for (size_t i = 0; i < roots.size(); ++i) {
+      const double delta = Refinement<R>::bound(sol, size_t(roots[i]), d, this->m_xspace->q_action_norms(),
+                                                this->m_xspace->d_action_norms(), refine_delta_scale(roots[i]));
+      m_refine.delta[size_t(roots[i])] = delta;
+      if (m_refine.triggers(errors[i], delta, this->m_convergence_threshold)) {
+        rroots.push_back(roots[i]);
+        rx.push_back(parameters[i]);
+        ra.push_back(action[i]);
+        slot.push_back(i);
+      }
+    }
+    if (rroots.empty()) return;
+    m_refine.hook(cwrap(rx.begin(), rx.end()), ra);
+    m_refine.stats.refined_actions += int(rroots.size());
+    if (m_refine.stats.first_refined_iteration == 0) m_refine.stats.first_refined_iteration = this->m_stats->iterations + 1;
+    this->m_residual_norms2.clear();
+    this->construct_residual(rroots, cwrap(rx.begin(), rx.end()), ra);
+    std::vector<double> e(rroots.size(), 0);
+    if (this->m_residual_norms2.size() == rroots.size()) {
+      for (size_t i = 0; i < e.size(); ++i) e[i] = std::sqrt(std::abs(this->m_residual_norms2[i]));
+    } else {
+      detail::update_errors(e, cwrap(ra.begin(), ra.end()), this->m_handlers->rr());
+    }
+    this->m_residual_norms2.clear();
+    for (size_t i = 0; i < e.size(); ++i) errors[slot[i]] = e[i];
+  }
+
   // reference propose_rspace.h:553-624
   std::vector<int> propose_rspace(const VecRef<R>& parameters, const VecRef<R>& residuals) {
     auto& xs = *this->m_xspace;
@@ -882,10 +837,10 @@ class DavidsonSolver : public IterativeSolverTemplate<R, Q, P> {
     // rebuilds in every iteration, and the residual then settles at a few times that loss.  So when the Q space
     // passes the limit it is cut back below it, by refine_dspace_slack() vectors: the limit holds as before, and
     // a rebuild comes once in several iterations, each loss decayed before the next.
-    if (!q_delete.empty() && this->m_refine && this->m_refine_dspace && !this->working_set().empty() &&
-        refine_dspace_slack() > 0)
+    const bool consistent = m_refine.options.on && m_refine.options.dspace;
+    if (!q_delete.empty() && consistent && !this->working_set().empty() && refine_dspace_slack() > 0)
       q_delete = detail::limit_qspace_size(xs.dimensions(), size_t(m_max_size_qspace - refine_dspace_slack()), solutions, log);
-    if (!q_delete.empty() && this->m_refine && this->m_refine_dspace) {
+    if (!q_delete.empty() && consistent) {
       // An empty working set ends the solve: nothing more is added, and a rebuild would round the converged
       // solutions once more after their (true) residuals were reported -- the subspace stays as it is.
       if (!this->working_set().empty()) {
@@ -899,7 +854,7 @@ class DavidsonSolver : public IterativeSolverTemplate<R, Q, P> {
       auto wdp = wrap(dp);
       auto wda = wrap(da);
       xs.update_dspace(wdp, wda);
-      this->m_dspace_rebuilds++;
+      m_refine.stats.dspace_rebuilds++;
       ss.solve(xs.data, solutions.rows());
     }
     auto wres = wrap(residuals.begin(), residuals.begin() + this->working_set().size());
@@ -927,13 +882,13 @@ class DavidsonSolver : public IterativeSolverTemplate<R, Q, P> {
     return detail::get_new_working_set(this->working_set(), cwrap(residuals), cwrap(wres));
   }
 
-  // The D space rebuilt in the refined mode (set_refine_dspace).  `parameters` are free until the end of
+  // The D space rebuilt in the refined mode (refine.h, options.dspace).  `parameters` are free until the end of
   // propose_rspace, which overwrites them (nothing reads them in between): they hold the new D parameters in
   // R's format; the actions get R vectors of their own for the duration.
   void rebuild_dspace_refined(const subspace::Matrix<double>& solutions, std::vector<int> q_delete, const VecRef<R>& parameters) {
     auto& xs = *this->m_xspace;
     auto& h = *this->m_handlers;
-    this->require_action_hook();
+    m_refine.require_hook();
     if (parameters.empty()) throw std::logic_error("refine_dspace: no parameter vectors to work in");
     std::vector<R> spare;  // where the caller gave fewer vectors than there are solutions
     spare.reserve(solutions.rows());
@@ -948,15 +903,15 @@ class DavidsonSolver : public IterativeSolverTemplate<R, Q, P> {
     act.reserve(nD);
     for (size_t i = 0; i < nD; ++i) act.emplace_back(detail::scratch_like(h.rr(), twin[i].get()));
     const auto w = cwrap(twin.begin(), twin.begin() + long(nD));
-    if (nD > 0) this->m_action_hook(w, wrap(act));
-    this->m_dspace_rebuilds++;
-    this->m_dspace_actions += int(nD);
+    if (nD > 0) m_refine.hook(w, wrap(act));
+    m_refine.stats.dspace_rebuilds++;
+    m_refine.stats.dspace_actions += int(nD);
     std::sort(q_delete.begin(), q_delete.end(), std::greater<int>());
     for (int iq : q_delete) xs.eraseq(size_t(iq));
     xs.update_dspace_refined(dp, w, cwrap(act));
   }
 
-  std::optional<int> m_refine_dspace_slack;  // set_refine_dspace_slack; unset: the default rule
+  Refinement<R> m_refine;
   int m_max_size_qspace = std::numeric_limits<int>::max();
   detail::DSpaceResetter<Q> m_resetter;
   bool m_hermiticity = false;
@@ -992,21 +947,6 @@ class LinearEigensystemDavidson : public DavidsonSolver<R, Q, P> {
   }
 
  protected:
-  // The refined mode's scope (IterativeSolverTemplate::set_refine): each limit is an error naming the option.
-  void check_refine() const override {
-    constexpr int unlimited = std::numeric_limits<int>::max();
-    if (!this->get_hermiticity()) throw std::runtime_error("refine: needs hermitian = 1 (hermiticity)");
-    if (this->get_max_size_qspace() != unlimited && !this->m_refine_dspace)
-      throw std::runtime_error("refine: max_size_qspace must be unlimited (a D space is not supported)");
-    if (this->get_reset_D() != unlimited) throw std::runtime_error("refine: reset_D must be off (a D space is not supported)");
-    // (set_max_size_qspace lowers reset_D_max_Q_size to the limit with it: that implied value is no request
-    // for a reset, which reset_D alone turns on.  A caller's own reset_D_max_Q_size equal to the limit cannot be
-    // told from it and passes too; it has no effect while reset_D is refused above.)
-    const bool implied = this->m_refine_dspace && this->get_reset_D_maxQ_size() == this->get_max_size_qspace();
-    if (this->get_reset_D_maxQ_size() != unlimited && !implied)
-      throw std::runtime_error("refine: reset_D_max_Q_size must be unlimited (a D space is not supported)");
-  }
-
   void set_value_errors() override {
     const auto cur = this->m_subspace_solver->eigenvalues();
     this->m_value_errors.assign(cur.size(), std::numeric_limits<double>::max());
@@ -1163,21 +1103,15 @@ class LinearEquationsDavidson : public DavidsonSolver<R, Q, P> {
   }
 
  protected:
-  // The refined mode (IterativeSolverTemplate::set_refine) for linear equations, in the scope of the eigensolver's
+  // The refined mode (refine.h) for linear equations, in the scope of the eigensolver's
   // without a D space; each limit is an error naming the option.  Beyond the shared steps it rests on two things:
   // every right-hand side has a twin in R's format (XSpace::rhs_r; set_refine goes before add_equations), which
   // the subspace rhs rows and the residuals read instead of the stored, rounded copy -- a residual against a
   // rounded b could be no better than 2^-24 |b| -- and the bound delta_i is divided by |b_i|, as the errors are.
-  void check_refine() const override {
-    constexpr int unlimited = std::numeric_limits<int>::max();
-    if (!this->get_hermiticity()) throw std::runtime_error("refine: needs hermitian = 1 (hermiticity)");
-    if (this->m_refine_dspace)
-      throw std::runtime_error("refine: refine_dspace (Q_REFINE_DSPACE) is not available for LinearEquations");
-    if (this->get_max_size_qspace() != unlimited)
-      throw std::runtime_error("refine: max_size_qspace must be unlimited (a D space is not supported)");
-    if (this->get_reset_D() != unlimited) throw std::runtime_error("refine: reset_D must be off (a D space is not supported)");
-    if (this->get_reset_D_maxQ_size() != unlimited)
-      throw std::runtime_error("refine: reset_D_max_Q_size must be unlimited (a D space is not supported)");
+  void check_refine_dspace() const override {
+    throw std::runtime_error("refine: refine_dspace (Q_REFINE_DSPACE) is not available for LinearEquations");
+  }
+  void check_refine_more() const override {
     if (const_cast<LinearEquationsDavidson*>(this)->get_augmented_hessian() != 0)
       throw std::runtime_error("refine: augmented_hessian must be 0 (its residual is not A x - b)");
     if (this->m_xspace->rhs_r().size() != this->m_xspace->rhs().size())
@@ -1194,7 +1128,7 @@ class LinearEquationsDavidson : public DavidsonSolver<R, Q, P> {
   // R's format, never the stored copy.
   void construct_residual(const std::vector<int>& roots, const CVecRef<R>& params, const VecRef<R>& actions) override {
     const auto& norm = this->m_xspace->rhs_norm();
-    const bool twins = this->m_refine;
+    const bool twins = this->refine();
     const auto stored = rhs();
     const auto exact = this->m_xspace->rhs_r();
     std::vector<double> s(roots.size(), 1.0);

@@ -235,11 +235,13 @@ class XSpace {
     auto nd = new_qspace_data(params, actions);
     qspace.update(params, actions, nd.qq, nd.qx, nd.xq, m_dim, data);
     // the new vectors are prepended in their order (QSpace::update), their action norms with them
-    if (m_refined) m_q_action_norms.insert(m_q_action_norms.begin(), m_new_action_norms.begin(), m_new_action_norms.end());
+    if (m_refined.on)
+      m_refined.q_action_norms.insert(m_refined.q_action_norms.begin(), m_refined.new_action_norms.begin(),
+                                      m_refined.new_action_norms.end());
     update_dimensions();
   }
 
-  // Refined mode (solvers.h, IterativeSolverTemplate::set_refine), for a Q space stored in a narrower
+  // Refined mode (refine.h), for a Q space stored in a narrower
   // format than R and new parameters that were rounded to that format BEFORE their action was computed:
   // the new rows of H come from the stored Q parameters and the new full-precision actions, never from the
   // stored (rounded) Q actions, so S and H are the projection onto the span of the stored parameters in the
@@ -248,26 +250,26 @@ class XSpace {
   void set_refined(bool on) {
     if (on && m_dim.nQ + m_dim.nD != 0) throw std::logic_error("refine: must be set on an empty subspace");
     // a right-hand side's twin in R's format cannot be rebuilt from its stored (rounded) copy
-    if (on && m_rhs_r.size() != m_rhs.size())
+    if (on && m_refined.rhs_r.size() != m_rhs.size())
       throw std::logic_error("refine: set_refine must be called before add_equations (the right-hand sides are "
                              "already stored rounded; call set_refine(true) first, then add_equations)");
-    if (!on) m_rhs_r.clear();
-    m_refined = on;
-    m_refined_dspace = false;
-    m_q_action_norms.clear();
-    m_d_action_norms.clear();
+    if (!on) m_refined.rhs_r.clear();
+    m_refined.on = on;
+    m_refined.dspace = false;
+    m_refined.q_action_norms.clear();
+    m_refined.d_action_norms.clear();
   }
-  bool refined() const { return m_refined; }
-  const std::vector<double>& q_action_norms() const { return m_q_action_norms; }
-  // The refined mode with a D space (solvers.h set_refine_dspace): the D space is then replaced by
+  bool refined() const { return m_refined.on; }
+  const std::vector<double>& q_action_norms() const { return m_refined.q_action_norms; }
+  // The refined mode with a D space (refine.h, DavidsonSolver::set_refine_dspace): the D space is then replaced by
   // update_dspace_refined only, whose stored actions are true actions of the stored parameters, and the refined
   // rows of new_qspace_data take the D columns from the stored D parameters as they do for Q.
   void set_refined_dspace(bool on) {
-    if (on && !m_refined) throw std::logic_error("refine: a consistent D space needs the refined mode");
-    m_refined_dspace = on;
+    if (on && !m_refined.on) throw std::logic_error("refine: a consistent D space needs the refined mode");
+    m_refined.dspace = on;
   }
-  bool refined_dspace() const { return m_refined_dspace; }
-  const std::vector<double>& d_action_norms() const { return m_d_action_norms; }
+  bool refined_dspace() const { return m_refined.dspace; }
+  const std::vector<double>& d_action_norms() const { return m_refined.d_action_norms; }
 
   // Replaces the D space in the refined mode.  params: the new stored D parameters; w[i]: params[i] in R's
   // format, exactly; a[i] = H w[i] in R's precision.  The stored D actions are the narrowing copies of a, their
@@ -275,7 +277,7 @@ class XSpace {
   // w and a against the stored parameters: S(D,D) = w.w, S(D,Q) = w.q, S(D,P), H(D,D) = w.a, H(Q,D) = q.a,
   // H(P,D) = p.a, H(D,Q) and H(D,P) their transposes (hermitian).  The stored Q actions are not read.
   void update_dspace_refined(std::vector<Q>& params, const CVecRef<R>& w, const CVecRef<R>& a) {
-    if (!m_refined || !m_refined_dspace) throw std::logic_error("refine: update_dspace_refined needs set_refined_dspace");
+    if (!m_refined.on || !m_refined.dspace) throw std::logic_error("refine: update_dspace_refined needs set_refined_dspace");
     if (!m_hermitian || m_action_dot_action) throw std::logic_error("refine: hermitian kernels only");
     const size_t nd = params.size();
     if (w.size() != nd || a.size() != nd) throw std::logic_error("update_dspace_refined: inconsistent container sizes");
@@ -288,7 +290,7 @@ class XSpace {
     update_dimensions();
     for (auto e : {EqnData::H, EqnData::S}) data[e].resize({m_dim.nX, m_dim.nX});
     data[EqnData::rhs].resize({m_dim.nX, m_dim.nRHS});
-    m_d_action_norms.assign(nd, 0.0);
+    m_refined.d_action_norms.assign(nd, 0.0);
     if (nd == 0) return;
     const auto& d = m_dim;
     const auto pp = cparamsp();
@@ -313,7 +315,7 @@ class XSpace {
           H(d.oQ + j, d.oD + i) = H(d.oD + i, d.oQ + j) = g(nd + i, cQ + j);
         }
         for (size_t j = 0; j < d.nRHS; ++j) data[EqnData::rhs](d.oD + i, j) = g(i, cR + j);
-        m_d_action_norms[i] = std::sqrt(std::abs(g(nd + i, cA + i)));
+        m_refined.d_action_norms[i] = std::sqrt(std::abs(g(nd + i, cA + i)));
       }
     } else {
       const auto sdd = util::overlap(w, h.rr());
@@ -329,7 +331,7 @@ class XSpace {
         }
       if (d.nRHS) data[EqnData::rhs].slice({d.oD, 0}, {d.oD + d.nD, d.nRHS}) = util::overlap(w, rhs_r(), h.rr());
       if constexpr (!std::is_same_v<R, Q>)  // (Q = R stores its actions exactly: no error to bound)
-        for (size_t i = 0; i < nd; ++i) m_d_action_norms[i] = std::sqrt(std::abs(h.rr().dot(a[i].get(), a[i].get())));
+        for (size_t i = 0; i < nd; ++i) m_refined.d_action_norms[i] = std::sqrt(std::abs(h.rr().dot(a[i].get(), a[i].get())));
     }
     if (d.nP) {  // the sparse rows: [w, a] against P in one inner product
       const auto gp = util::overlap(rows, pp, h.rp());
@@ -343,10 +345,10 @@ class XSpace {
 
   // Replaces the D space and recomputes its blocks of S and H (reference XSpace.h:174-187).
   void update_dspace(VecRef<Q>& params, VecRef<Q>& actions) {
-    if (m_refined && !params.empty())
+    if (m_refined.on && !params.empty())
       throw std::runtime_error("refine: a D space is not supported (its stored pairs are rounded combinations)");
     dspace.update(params, actions);
-    m_d_action_norms.clear();
+    m_refined.d_action_norms.clear();
     update_dimensions();
     for (auto e : {EqnData::H, EqnData::S}) data[e].resize({m_dim.nX, m_dim.nX});
     auto& hqq = m_handlers->qq();
@@ -403,8 +405,8 @@ class XSpace {
   void add_rhs_equations(const CVecRef<R>& rhs_) {
     for (const auto& r : rhs_) m_rhs.emplace_back(m_handlers->qr().copy(r));
     // refined mode: the twin in R's format, which every use of a right-hand side then reads instead
-    if (m_refined)
-      for (const auto& r : rhs_) m_rhs_r.emplace_back(m_handlers->rr().copy(r));
+    if (m_refined.on)
+      for (const auto& r : rhs_) m_refined.rhs_r.emplace_back(m_handlers->rr().copy(r));
     for (const auto& r : rhs_) {
       const double d = std::abs(m_handlers->rr().dot(r, r));
       if (d == 0) throw std::runtime_error("RHS vector cannot be zero");
@@ -417,11 +419,11 @@ class XSpace {
   const std::vector<double>& rhs_norm() const { return m_rhs_norm; }
   //! The right-hand sides in R's format, kept in the refined mode only (set_refined); empty otherwise.  The
   //! refined mode reads these wherever the other reads rhs(): the subspace rhs rows and the residuals.
-  CVecRef<R> rhs_r() const { return cwrap(m_rhs_r); }
+  CVecRef<R> rhs_r() const { return cwrap(m_refined.rhs_r); }
 
   void eraseq(size_t i) {
     qspace.erase(i);
-    if (m_refined) m_q_action_norms.erase(m_q_action_norms.begin() + long(i));
+    if (m_refined.on) m_refined.q_action_norms.erase(m_refined.q_action_norms.begin() + long(i));
     remove_data(m_dim.oQ + i);
     update_dimensions();
   }
@@ -432,7 +434,7 @@ class XSpace {
   }
   void erased(size_t i) {
     dspace.erase(i);
-    if (m_refined && i < m_d_action_norms.size()) m_d_action_norms.erase(m_d_action_norms.begin() + long(i));
+    if (m_refined.on && i < m_refined.d_action_norms.size()) m_refined.d_action_norms.erase(m_refined.d_action_norms.begin() + long(i));
     remove_data(m_dim.oD + i);
     update_dimensions();
   }
@@ -453,19 +455,146 @@ class XSpace {
   DSpace<Q> dspace;
 
  private:
-  // reference xspace::update_qspace_data (XSpace.h:30-83)
+  // Where the blocks of a batched-row matrix g sit.  Its rows are the new parameters (then, in the refined mode,
+  // the new actions); its columns are the blocks [params, actions, Q params, Q actions, D params, D actions, rhs]
+  // in the order the mode lists them.  S(new, .) comes from row i; H(new, Q/D) from row h_row + i and the columns
+  // hQ, hD: the stored Q/D actions against the parameter rows (plain), or the stored Q/D parameters against the
+  // action rows (refined: the stored actions are not read).
+  struct RowLayout {
+    size_t actions, q, d, rhs;  // the columns of H(new, new), S(new, Q), S(new, D) and the rhs rows
+    size_t h_row, hq, hd;       // H(new, Q) = g(h_row + i, hq + j), H(new, D) = g(h_row + i, hd + j)
+  };
+  void scatter_rows(const Matrix<double>& g, const RowLayout& c, size_t nn, NewData& nd) const {
+    const auto& d = m_dim;
+    for (size_t i = 0; i < nn; ++i) {
+      for (size_t j = 0; j <= i; ++j) nd.qq[EqnData::S](i, j) = nd.qq[EqnData::S](j, i) = g(i, j);
+      for (size_t j = 0; j < nn; ++j) nd.qq[EqnData::H](i, j) = g(i, c.actions + j);
+      for (size_t j = 0; j < d.nQ; ++j) {
+        nd.qx[EqnData::S](i, d.oQ + j) = g(i, c.q + j);
+        nd.qx[EqnData::H](i, d.oQ + j) = g(c.h_row + i, c.hq + j);
+      }
+      for (size_t j = 0; j < d.nD; ++j) {
+        nd.qx[EqnData::S](i, d.oD + j) = g(i, c.d + j);
+        nd.qx[EqnData::H](i, d.oD + j) = g(c.h_row + i, c.hd + j);
+      }
+      for (size_t j = 0; j < m_rhs.size(); ++j) nd.qq[EqnData::rhs](i, j) = g(i, c.rhs + j);
+    }
+  }
+  // The same for action . action (DIIS), which has two matrices and a symmetric H(new, new): the S rows g from
+  // the parameters ([params, Q params, D params, rhs]) and the H rows ga from the actions ([actions, Q actions,
+  // D actions]).  (Kept apart from scatter_rows, as update_dspace_refined's scatter into the D blocks is: one
+  // function for all would branch on its caller.)
+  void scatter_rows_ada(const Matrix<double>& g, const Matrix<double>& ga, size_t nn, NewData& nd) const {
+    const auto& d = m_dim;
+    const size_t cQ = nn, cD = cQ + d.nQ, cR = cD + d.nD;
+    for (size_t i = 0; i < nn; ++i) {
+      for (size_t j = 0; j <= i; ++j) {
+        nd.qq[EqnData::S](i, j) = nd.qq[EqnData::S](j, i) = g(i, j);
+        nd.qq[EqnData::H](i, j) = nd.qq[EqnData::H](j, i) = ga(i, j);
+      }
+      for (size_t j = 0; j < d.nQ; ++j) {
+        nd.qx[EqnData::S](i, d.oQ + j) = g(i, cQ + j);
+        nd.qx[EqnData::H](i, d.oQ + j) = ga(i, nn + j);
+      }
+      for (size_t j = 0; j < d.nD; ++j) {
+        nd.qx[EqnData::S](i, d.oD + j) = g(i, cD + j);
+        nd.qx[EqnData::H](i, d.oD + j) = ga(i, nn + d.nQ + j);
+      }
+      for (size_t j = 0; j < m_rhs.size(); ++j) nd.qq[EqnData::rhs](i, j) = g(i, cR + j);
+    }
+  }
+
+  // Every block whose rows are the new parameters as batched overlaps, where the handler of the current mode has
+  // them.  False where it declines: the blocks are then still to be computed call by call.
+  bool batched_rows(const CVecRef<R>& params, const CVecRef<R>& actions, bool refined_rows, NewData& nd) {
+    auto& h = *m_handlers;
+    const auto& d = m_dim;
+    const size_t nn = params.size(), nr = m_rhs.size();
+    if (nn == 0) return false;
+    const auto qp = cparamsq(), qa = cactionsq(), dp = cparamsd(), da = cactionsd();
+    // one batched overlap of `rows` with the columns rcols, then qcols: array::fused_overlap_rows for Q = R, and
+    // for R and Q in containers of their own array::fused_overlap_rows_mixed, the two lists apart
+    auto overlap_rows = [&h](const CVecRef<R>& rows, std::vector<CVecRef<R>> rcols, const std::vector<CVecRef<Q>>& qcols,
+                             Matrix<double>& out) {
+      using array::fused_overlap_rows;
+      using array::fused_overlap_rows_mixed;
+      if constexpr (std::is_same_v<R, Q>) {
+        rcols.insert(rcols.end(), qcols.begin(), qcols.end());
+        return fused_overlap_rows(h.rr(), rows, rcols, out);
+      } else {
+        return fused_overlap_rows_mixed(h.rq(), rows, rcols, qcols, out);
+      }
+    };
+    Matrix<double> g, ga;
+    if (refined_rows) {
+      // rows [params, actions] against the f64 columns [params, actions, rhs twins (rhs_r)] and the stored
+      // columns [Q params, D params]: S(new, .) from the params rows, H(new, new) = params . actions, H(Q, new)
+      // and H(D, new) from the actions rows against the stored parameters (the products of the non-hermitian
+      // branch of new_qspace_data), and the diagonal actions . actions for the norms.
+      CVecRef<R> rows(params.begin(), params.end());
+      rows.insert(rows.end(), actions.begin(), actions.end());
+      if (!overlap_rows(rows, {params, actions, rhs_r()}, {qp, dp}, g)) return false;
+      const size_t cR = 2 * nn, cQ = cR + nr, cD = cQ + d.nQ;
+      scatter_rows(g, RowLayout{nn, cQ, cD, cR, nn, cQ, cD}, nn, nd);
+      for (size_t i = 0; i < nn; ++i) m_refined.new_action_norms[i] = std::sqrt(std::abs(g(nn + i, nn + i)));
+    } else if (m_action_dot_action) {
+      // two batched overlaps: [params, Q params, D params, rhs] and [actions, Q actions, D actions]
+      if (!overlap_rows(params, {params}, {qp, dp, rhs()}, g) || !overlap_rows(actions, {actions}, {qa, da}, ga)) return false;
+      scatter_rows_ada(g, ga, nn, nd);
+    } else {
+      // one batched overlap: columns [params, actions, Q params, Q actions, D params, D actions, rhs]
+      if (!overlap_rows(params, {params, actions}, {qp, qa, dp, da, rhs()}, g)) return false;
+      const size_t cQ = 2 * nn, cQA = cQ + d.nQ, cD = cQA + d.nQ, cDA = cD + d.nD, cR = cDA + d.nD;
+      scatter_rows(g, RowLayout{nn, cQ, cD, cR, 0, cQA, cDA}, nn, nd);
+    }
+    return true;
+  }
+
+  // The same blocks call by call (reference xspace::update_qspace_data, XSpace.h:30-83).
+  void rows_call_by_call(const CVecRef<R>& params, const CVecRef<R>& actions, NewData& nd) {
+    auto& h = *m_handlers;
+    const auto& d = m_dim;
+    const size_t nn = params.size();
+    const auto qp = cparamsq(), qa = cactionsq(), dp = cparamsd(), da = cactionsd();
+    const auto& lhs_h = m_action_dot_action ? actions : params;
+    nd.qq[EqnData::S] = util::overlap(params, h.rr());
+    nd.qx[EqnData::S].slice({0, d.oQ}, {nn, d.oQ + d.nQ}) = util::overlap(params, qp, h.rq());
+    nd.qx[EqnData::S].slice({0, d.oD}, {nn, d.oD + d.nD}) = util::overlap(params, dp, h.rq());
+    nd.qq[EqnData::H] = m_action_dot_action ? util::overlap(actions, h.rr()) : util::overlap(params, actions, h.rr());
+    nd.qx[EqnData::H].slice({0, d.oQ}, {nn, d.oQ + d.nQ}) = util::overlap(lhs_h, qa, h.rq());
+    nd.qx[EqnData::H].slice({0, d.oD}, {nn, d.oD + d.nD}) = util::overlap(lhs_h, da, h.rq());
+    nd.qq[EqnData::rhs] = util::overlap(params, rhs(), h.rq());
+  }
+  // ... and of the refined rows (batched_rows): the stored Q and D actions are not read.
+  void refined_rows_call_by_call(const CVecRef<R>& params, const CVecRef<R>& actions, NewData& nd) {
+    auto& h = *m_handlers;
+    const auto& d = m_dim;
+    const size_t nn = params.size();
+    const auto qp = cparamsq(), dp = cparamsd();
+    nd.qq[EqnData::S] = util::overlap(params, h.rr());
+    nd.qx[EqnData::S].slice({0, d.oQ}, {nn, d.oQ + d.nQ}) = util::overlap(params, qp, h.rq());
+    nd.qq[EqnData::H] = util::overlap(params, actions, h.rr());
+    nd.qx[EqnData::H].slice({0, d.oQ}, {nn, d.oQ + d.nQ}) = util::overlap(actions, qp, h.rq());
+    if (d.nD) {
+      nd.qx[EqnData::S].slice({0, d.oD}, {nn, d.oD + d.nD}) = util::overlap(params, dp, h.rq());
+      nd.qx[EqnData::H].slice({0, d.oD}, {nn, d.oD + d.nD}) = util::overlap(actions, dp, h.rq());
+    }
+    nd.qq[EqnData::rhs] = util::overlap(params, rhs_r(), h.rr());
+    for (size_t i = 0; i < nn; ++i)
+      m_refined.new_action_norms[i] = std::sqrt(std::abs(h.rr().dot(actions[i].get(), actions[i].get())));
+  }
+
+  // The new rows and columns of S, H and rhs for new parameters: the P rows, the dense rows (batched_rows, or
+  // call by call), and what follows from them by symmetry.
   NewData new_qspace_data(const CVecRef<R>& params, const CVecRef<R>& actions) {
     auto& h = *m_handlers;
     const auto& d = m_dim;
     const size_t nn = params.size();
     NewData nd(nn, d.nX, m_rhs.size());
-    auto& qq = nd.qq;
     auto& qx = nd.qx;
     auto& xq = nd.xq;
     const auto pp = cparamsp();
-    const auto qp = cparamsq(), qa = cactionsq(), dp = cparamsd(), da = cactionsd();
-    const auto& lhs_h = m_action_dot_action ? actions : params;
-    bool fused = false;
+    const auto qp = cparamsq(), dp = cparamsd();
     // S(R, P) and H(P, R) as one sparse inner product over [params, actions] (one launch, one
     // reduction; each element is the same sum over its P vector's entries either way), queued ahead of
     // the dense rows where the handler can (array::queued_overlap): the wait for those covers it
@@ -479,136 +608,17 @@ class XSpace {
         p_rows = queued_overlap(h.rp(), both, pp);
       }
     }
-    // The batched rows g (columns [params, actions, Q params, Q actions, D params, D actions, rhs]) into
-    // the new data; for action . action (DIIS) the S rows g from the parameters ([params, Q params,
-    // D params, rhs]) and the H rows ga from the actions ([actions, Q actions, D actions]).
-    auto take_rows = [&](const Matrix<double>& g) {
-      const size_t cA = nn, cQ = 2 * nn, cQA = cQ + d.nQ, cD = cQA + d.nQ, cDA = cD + d.nD, cR = cDA + d.nD;
-      for (size_t i = 0; i < nn; ++i) {
-        for (size_t j = 0; j <= i; ++j) qq[EqnData::S](i, j) = qq[EqnData::S](j, i) = g(i, j);
-        for (size_t j = 0; j < nn; ++j) qq[EqnData::H](i, j) = g(i, cA + j);
-        for (size_t j = 0; j < d.nQ; ++j) {
-          qx[EqnData::S](i, d.oQ + j) = g(i, cQ + j);
-          qx[EqnData::H](i, d.oQ + j) = g(i, cQA + j);
-        }
-        for (size_t j = 0; j < d.nD; ++j) {
-          qx[EqnData::S](i, d.oD + j) = g(i, cD + j);
-          qx[EqnData::H](i, d.oD + j) = g(i, cDA + j);
-        }
-        for (size_t j = 0; j < m_rhs.size(); ++j) qq[EqnData::rhs](i, j) = g(i, cR + j);
-      }
-    };
-    auto take_rows_ada = [&](const Matrix<double>& g, const Matrix<double>& ga) {
-      const size_t cQ = nn, cD = cQ + d.nQ, cR = cD + d.nD;
-      for (size_t i = 0; i < nn; ++i) {
-        for (size_t j = 0; j <= i; ++j) {
-          qq[EqnData::S](i, j) = qq[EqnData::S](j, i) = g(i, j);
-          qq[EqnData::H](i, j) = qq[EqnData::H](j, i) = ga(i, j);
-        }
-        for (size_t j = 0; j < d.nQ; ++j) {
-          qx[EqnData::S](i, d.oQ + j) = g(i, cQ + j);
-          qx[EqnData::H](i, d.oQ + j) = ga(i, nn + j);
-        }
-        for (size_t j = 0; j < d.nD; ++j) {
-          qx[EqnData::S](i, d.oD + j) = g(i, cD + j);
-          qx[EqnData::H](i, d.oD + j) = ga(i, nn + d.nQ + j);
-        }
-        for (size_t j = 0; j < m_rhs.size(); ++j) qq[EqnData::rhs](i, j) = g(i, cR + j);
-      }
-    };
-    if (m_refined) m_new_action_norms.assign(nn, 0.0);  // (Q = R stores its actions exactly: no error to bound)
-    if constexpr (std::is_same_v<R, Q>) {
-      // every block whose rows are the new parameters, as one batched overlap where the handler has
-      // it: columns [params, actions, Q params, Q actions, D params, D actions, rhs]
-      Matrix<double> g;
-      using array::fused_overlap_rows;
-      if (!m_action_dot_action && nn > 0 &&
-          fused_overlap_rows(h.rr(), params, std::vector<CVecRef<R>>{params, actions, qp, qa, dp, da, rhs()}, g)) {
-        fused = true;
-        take_rows(g);
-      }
-      // action . action (DIIS): the S rows from the parameters, the H rows from the actions -- two
-      // batched overlaps: [params, Q params, D params, rhs] and [actions, Q actions, D actions]
-      Matrix<double> ga;
-      if (m_action_dot_action && nn > 0 &&
-          fused_overlap_rows(h.rr(), params, std::vector<CVecRef<R>>{params, qp, dp, rhs()}, g) &&
-          fused_overlap_rows(h.rr(), actions, std::vector<CVecRef<R>>{actions, qa, da}, ga)) {
-        fused = true;
-        take_rows_ada(g, ga);
-      }
-    } else {
-      // R and Q in containers of their own: the same column sets, the R columns and the Q columns as
-      // two lists, where the R x Q handler has the batched form (array::fused_overlap_rows_mixed)
-      Matrix<double> g;
-      using array::fused_overlap_rows_mixed;
-      if (m_refined) {
-        // rows [params, actions] against the f64 columns [params, actions] and the stored columns
-        // [Q params, rhs]: S(new, .) from the params rows, H(new, new) = params . actions, H(Q, new) from the
-        // actions rows against the Q params (the products of the non-hermitian branch below), and the
-        // diagonal actions . actions for the norms; the stored Q actions are not read.  A D space
-        // (set_refined_dspace: its stored actions are true actions) adds its parameters to the stored columns
-        // and takes S(new, D), H(new, D) from the same rows as for Q.
-        if (!m_hermitian || m_action_dot_action) throw std::logic_error("refine: hermitian kernels only");
-        if (d.nD != 0 && !m_refined_dspace) throw std::runtime_error("refine: a D space is not supported");
-        CVecRef<R> rows(params.begin(), params.end());
-        rows.insert(rows.end(), actions.begin(), actions.end());
-        // Right-hand sides (linear equations) are f64 columns too: their twins in R's format (rhs_r).
-        if (nn > 0 && fused_overlap_rows_mixed(h.rq(), rows, std::vector<CVecRef<R>>{params, actions, rhs_r()},
-                                               std::vector<CVecRef<Q>>{qp, dp}, g)) {
-          const size_t cA = nn, cR = 2 * nn, cQ = cR + m_rhs.size(), cD = cQ + d.nQ;
-          for (size_t i = 0; i < nn; ++i) {
-            for (size_t j = 0; j <= i; ++j) qq[EqnData::S](i, j) = qq[EqnData::S](j, i) = g(i, j);
-            for (size_t j = 0; j < nn; ++j) qq[EqnData::H](i, j) = g(i, cA + j);
-            for (size_t j = 0; j < d.nQ; ++j) {
-              qx[EqnData::S](i, d.oQ + j) = g(i, cQ + j);
-              qx[EqnData::H](i, d.oQ + j) = g(nn + i, cQ + j);
-            }
-            for (size_t j = 0; j < d.nD; ++j) {
-              qx[EqnData::S](i, d.oD + j) = g(i, cD + j);
-              qx[EqnData::H](i, d.oD + j) = g(nn + i, cD + j);
-            }
-            for (size_t j = 0; j < m_rhs.size(); ++j) qq[EqnData::rhs](i, j) = g(i, cR + j);
-            m_new_action_norms[i] = std::sqrt(std::abs(g(nn + i, cA + i)));
-          }
-        } else {
-          qq[EqnData::S] = util::overlap(params, h.rr());
-          qx[EqnData::S].slice({0, d.oQ}, {nn, d.oQ + d.nQ}) = util::overlap(params, qp, h.rq());
-          qq[EqnData::H] = util::overlap(params, actions, h.rr());
-          qx[EqnData::H].slice({0, d.oQ}, {nn, d.oQ + d.nQ}) = util::overlap(actions, qp, h.rq());
-          if (d.nD) {
-            qx[EqnData::S].slice({0, d.oD}, {nn, d.oD + d.nD}) = util::overlap(params, dp, h.rq());
-            qx[EqnData::H].slice({0, d.oD}, {nn, d.oD + d.nD}) = util::overlap(actions, dp, h.rq());
-          }
-          qq[EqnData::rhs] = util::overlap(params, rhs_r(), h.rr());
-          for (size_t i = 0; i < nn; ++i)
-            m_new_action_norms[i] = std::sqrt(std::abs(h.rr().dot(actions[i].get(), actions[i].get())));
-        }
-        fused = true;  // the blocks are in place either way
-      }
-      if (!m_refined && !m_action_dot_action && nn > 0 &&
-          fused_overlap_rows_mixed(h.rq(), params, std::vector<CVecRef<R>>{params, actions},
-                                   std::vector<CVecRef<Q>>{qp, qa, dp, da, rhs()}, g)) {
-        fused = true;
-        take_rows(g);
-      }
-      Matrix<double> ga;
-      if (m_action_dot_action && nn > 0 &&
-          fused_overlap_rows_mixed(h.rq(), params, std::vector<CVecRef<R>>{params},
-                                   std::vector<CVecRef<Q>>{qp, dp, rhs()}, g) &&
-          fused_overlap_rows_mixed(h.rq(), actions, std::vector<CVecRef<R>>{actions}, std::vector<CVecRef<Q>>{qa, da},
-                                   ga)) {
-        fused = true;
-        take_rows_ada(g, ga);
-      }
+    if (m_refined.on) m_refined.new_action_norms.assign(nn, 0.0);  // (Q = R stores its actions exactly: no error to bound)
+    // The refined rows, for R and Q in containers of their own: hermitian, and a D space only where its stored
+    // actions are true actions (set_refined_dspace).
+    const bool refined_rows = m_refined.on && !std::is_same_v<R, Q>;
+    if (refined_rows) {
+      if (!m_hermitian || m_action_dot_action) throw std::logic_error("refine: hermitian kernels only");
+      if (d.nD != 0 && !m_refined.dspace) throw std::runtime_error("refine: a D space is not supported");
     }
-    if (!fused) {
-      qq[EqnData::S] = util::overlap(params, h.rr());
-      qx[EqnData::S].slice({0, d.oQ}, {nn, d.oQ + d.nQ}) = util::overlap(params, qp, h.rq());
-      qx[EqnData::S].slice({0, d.oD}, {nn, d.oD + d.nD}) = util::overlap(params, dp, h.rq());
-      qq[EqnData::H] = m_action_dot_action ? util::overlap(actions, h.rr()) : util::overlap(params, actions, h.rr());
-      qx[EqnData::H].slice({0, d.oQ}, {nn, d.oQ + d.nQ}) = util::overlap(lhs_h, qa, h.rq());
-      qx[EqnData::H].slice({0, d.oD}, {nn, d.oD + d.nD}) = util::overlap(lhs_h, da, h.rq());
-      qq[EqnData::rhs] = util::overlap(params, rhs(), h.rq());
+    if (!batched_rows(params, actions, refined_rows, nd)) {
+      if (refined_rows) refined_rows_call_by_call(params, actions, nd);
+      else rows_call_by_call(params, actions, nd);
     }
     bool p_rows_done = false;
     if constexpr (array::batched_symmetric_overlap<R>::value) {
@@ -636,8 +646,8 @@ class XSpace {
     transpose_copy(xq[EqnData::S].slice({d.oQ, 0}, {d.oQ + d.nQ, nn}), qx[EqnData::S].slice({0, d.oQ}, {nn, d.oQ + d.nQ}));
     transpose_copy(xq[EqnData::S].slice({d.oD, 0}, {d.oD + d.nD, nn}), qx[EqnData::S].slice({0, d.oD}, {nn, d.oD + d.nD}));
     if (m_logger->data_dump) {
-      m_logger->msg("Sqq = " + as_string(qq[EqnData::S]), Logger::Info);
-      m_logger->msg("Hqq = " + as_string(qq[EqnData::H]), Logger::Info);
+      m_logger->msg("Sqq = " + as_string(nd.qq[EqnData::S]), Logger::Info);
+      m_logger->msg("Hqq = " + as_string(nd.qq[EqnData::H]), Logger::Info);
     }
     return nd;
   }
@@ -649,7 +659,7 @@ class XSpace {
   void update_rhs_with_pspace() {
     data[EqnData::rhs].resize({m_dim.nP, m_dim.nRHS});
     if (m_dim.nP && m_dim.nRHS)
-      data[EqnData::rhs] = m_refined ? util::overlap(cparamsp(), rhs_r(), m_handlers->rp())
+      data[EqnData::rhs] = m_refined.on ? util::overlap(cparamsp(), rhs_r(), m_handlers->rp())
                                      : util::overlap(cparamsp(), rhs(), m_handlers->qp());
   }
   void remove_data(size_t i) {
@@ -662,15 +672,18 @@ class XSpace {
   std::shared_ptr<Logger> m_logger;
   Dimensions m_dim;
   std::vector<Q> m_rhs;
-  std::vector<R> m_rhs_r;  // refined mode: every right-hand side in R's format (rhs_r)
   std::vector<double> m_rhs_norm;
   bool m_hermitian = false;
   bool m_action_dot_action = false;
-  bool m_refined = false;
-  bool m_refined_dspace = false;
-  std::vector<double> m_q_action_norms;    // |a_j| per Q vector, Q order
-  std::vector<double> m_d_action_norms;    // |a_d| per D vector, D order (update_dspace_refined)
-  std::vector<double> m_new_action_norms;  // the same of the vectors new_qspace_data was last called with
+  // What the refined mode (set_refined) keeps beside the subspace
+  struct Refined {
+    bool on = false;
+    bool dspace = false;                    // set_refined_dspace
+    std::vector<R> rhs_r;                   // every right-hand side in R's format (rhs_r)
+    std::vector<double> q_action_norms;     // |a_j| per Q vector, Q order
+    std::vector<double> d_action_norms;     // |a_d| per D vector, D order (update_dspace_refined)
+    std::vector<double> new_action_norms;   // the same of the vectors new_qspace_data was last called with
+  } m_refined;
 };
 
 }  // namespace molpro::linalg::itsolv::subspace

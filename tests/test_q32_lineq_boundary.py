@@ -151,10 +151,10 @@ bool solve(const itsolv::Problem<hbm::Vec, hbm::SparseP>& problem, std::vector<h
 }
 void run(const itsolv::Problem<hbm::Vec, hbm::SparseP>& problem, std::vector<hbm::Vec>& b, const itsolv_options& o,
          itsolv_result& out) {
-  const double kappa = 0;
-  itsolv::problems::RefineStats stats;
+  const itsolv::RefineOptions refine{true, 0};  // kappa <= 0: the default
+  itsolv::RefineStats stats;
   itsolv::problems::run_linear_equations<hbm::Vec, hbm::VecF32, hbm::SparseP>(hbm::make_handlers_q32(), problem, {}, b, {},
-                                                                             o, out, {}, &kappa, &stats);
+                                                                             o, out, {}, &refine, &stats);
 }
 """
 

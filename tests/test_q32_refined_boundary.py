@@ -116,10 +116,10 @@ bool solve(const itsolv::Problem<hbm::Vec, hbm::SparseP>& problem, std::vector<h
   return ok && solver.refined_actions() >= 0 && solver.first_refined_iteration() >= 0 && solver.refine_delta().empty();
 }
 void run(const itsolv::Problem<hbm::Vec, hbm::SparseP>& problem, const itsolv_options& o, itsolv_result& out) {
-  const double kappa = 0;
-  itsolv::problems::RefineStats stats;
+  const itsolv::RefineOptions refine{true, 0};  // kappa <= 0: the default
+  itsolv::RefineStats stats;
   itsolv::problems::run_davidson<hbm::Vec, hbm::VecF32, hbm::SparseP>(hbm::make_handlers_q32(), problem, {}, {}, o, out,
-                                                                     {}, {}, &kappa, &stats);
+                                                                     {}, {}, &refine, &stats);
 }
 """
 

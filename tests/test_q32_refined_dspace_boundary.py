@@ -139,10 +139,10 @@ bool solve(const itsolv::Problem<hbm::Vec, hbm::SparseP>& problem, std::vector<h
   return ok && solver.refine_dspace() && solver.dspace_rebuilds() >= 0 && solver.dspace_actions() >= 0;
 }
 void run(const itsolv::Problem<hbm::Vec, hbm::SparseP>& problem, const itsolv_options& o, itsolv_result& out) {
-  const double kappa = 0;
-  itsolv::problems::RefineStats stats;
+  const itsolv::RefineOptions refine{true, 0, true};  // kappa <= 0: the default; with the consistent D space
+  itsolv::RefineStats stats;
   itsolv::problems::run_davidson<hbm::Vec, hbm::VecF32, hbm::SparseP>(hbm::make_handlers_q32(), problem, {}, {}, o, out,
-                                                                     {}, {}, &kappa, &stats, true);
+                                                                     {}, {}, &refine, &stats);
 }
 """
 
