@@ -175,6 +175,11 @@ int ssp_ledger_entry(ssp_ctx* ctx, int i, const char** name, long long* calls, d
  * returned; ssp_free launches the pending gemm_outer before the block returns to the arena, and
  * ssp_ctx_destroy discards it.  In the ledger the launch is a "gemm_outer" / "gemm_outer_set" row of
  * 8 n (k + m + e) bytes for e attached terms, which have no "axpy" row.
+ * When the call that launches it is ssp_dot(y, y, n) on one of at most 8 pending destinations, the launch
+ * also sums the squares of every destination, and that dot and the same dot of the other destinations are
+ * answered from those sums (the bits the dot itself gives, no "dot" row) until any other call of the
+ * context; foreign code that writes vector memory in between must take ssp_ctx_stream or call
+ * ssp_synchronize first, as above, which also drops the sums.  SSP_OUTER_NORMS=0 at ssp_ctx_create: off.
  * SSP_DEFER_OUTER=0 in the environment at ssp_ctx_create: every gemm_outer is launched at once. */
 int ssp_fill(ssp_ctx* ctx, double alpha, double* x, size_t n);
 /* x[:] *= alpha                        reference ArrayHandlerIterable.h:54-57 */

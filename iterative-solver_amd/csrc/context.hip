@@ -484,6 +484,7 @@ int ssp_ctx_create(int device, ssp_ctx** out) {
   if (const char* sm = std::getenv("SSP_SYNTH_MERGE")) ctx->synth_merge = std::atoi(sm) != 0;
   if (const char* df = std::getenv("SSP_DEFER_FILL")) ctx->defer_fill = std::atoi(df) != 0;
   if (const char* dout = std::getenv("SSP_DEFER_OUTER")) ctx->defer_outer = std::atoi(dout) != 0;
+  if (const char* on = std::getenv("SSP_OUTER_NORMS")) ctx->outer_norms_on = std::atoi(on) != 0;
   if (const char* ct = std::getenv("SSP_COMM_TIMEOUT_S")) {
     const double v = std::atof(ct);
     if (v > 0) ctx->comm_timeout_s = v;
@@ -526,6 +527,7 @@ int ssp_ctx_destroy(ssp_ctx* ctx) {
   for (auto& b : ctx->free_blocks) (void)hipFree(b.second);
   for (auto& b : ctx->live_blocks) (void)hipFree(b.first);
   if (ctx->partial) (void)hipFree(ctx->partial);
+  if (ctx->norms_dev) (void)hipFree(ctx->norms_dev);
   if (ctx->result_dev) (void)hipFree(ctx->result_dev);
   if (ctx->result_host) (void)hipHostFree(ctx->result_host);
   if (ctx->pub_flag) (void)hipHostFree(ctx->pub_flag);

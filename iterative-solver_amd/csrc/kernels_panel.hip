@@ -355,6 +355,10 @@ struct OuterArgs {
   const double* scale_dev;         // SC: deferred scales, sources [0, k) then destinations [k, k + m)
   double alpha[ssp::kOuterAlpha];  // alpha[i*m + j] in the argument block
   double epi[ssp::kOuterDst];
+  // NRM: per-workgroup sums of squares partial[b * m + j], folded by `tail` (nout = m).  At the end of
+  // the block, for the same reason.
+  double* partial;
+  ssp::FoldTail tail;
 };
 static_assert(sizeof(OuterArgs) <= 4000, "kernel argument block too large");
 static_assert(ssp::PendingOuter::kSrc == ssp::kOuterSrc && ssp::PendingOuter::kDst == ssp::kOuterDst,
@@ -367,6 +371,7 @@ static_assert(ssp::PendingOuter::kSrc == ssp::kOuterSrc && ssp::PendingOuter::kD
 // once, with nontemporal accesses (tools/mb_stream.hip: 5.35 TB/s against 4.8 for one position per
 // lane and plain accesses).
 constexpr int kOuterWin = 4;
+static_assert(kOuterWin == ssp::kDotU, "the norm-carrying instance walks k_dot_partial's windows");
 
 // SET (a.set = 1) is a separate instantiation: the write-only construct_solution form shows under its
 // own name in rocprofv3 statistics, so its launches are not averaged with the read-modify-write ones.
@@ -376,9 +381,25 @@ constexpr int kOuterWin = 4;
 // a.epi_mask is stored, epi[j] * x[k + j] is added to its finished sum by the fma k_axpy_win would have
 // done on the stored value.  Unmasked destinations take no term: fma(0, x, acc) would turn a -0.0 sum
 // into +0.0 and an infinite x into NaN.
-template <int M, bool DEV, bool SET, bool SC = false, bool EPI = false>
+// NRM (the record launched by the ssp_dot(y, y) of one of its destinations, outer_norms.h): next to the
+// stores, the sum of squares of every destination as stored, in the bits k_dot_partial<true, false> and
+// its fold give on the stored vector.  The launch takes that kernel's grid and its walk: whole windows in
+// the window loop (window position u into accumulator u: fma(v.x, v.x, .), fma(v.y, v.y, .)), then the
+// positions past the last whole window one per thread of workgroup 0 and the odd last element in its
+// thread 0, both into accumulator 0; (s0 + s1) + (s2 + s3), block_sum256's tree, partial[b * m + j],
+// ssp::fold_tail.  The stored elements do not depend on the thread that forms them.  The 4 M
+// accumulators per lane live in LDS ([j][u][thread]: every lane its own bank pair, 8 M KiB per
+// workgroup), not in 8 M more VGPRs, which would halve the M = 8 instance's waves per SIMD.
+template <int M>
+__device__ __forceinline__ double* outer_norm_acc() {
+  __shared__ double acc[M * kOuterWin * kBlock];
+  return acc;
+}
+
+template <int M, bool DEV, bool SET, bool SC = false, bool EPI = false, bool NRM = false>
 __global__ __launch_bounds__(kBlock) void k_gemm_outer(const OuterArgs a) {
   static_assert(!EPI || (SET && !SC), "the epilogue rides on the unscaled write-only form");
+  static_assert(!NRM || (SET && !SC && M <= 8), "the norms ride on the unscaled write-only form, 4-position windows");
   using ssp::ld2nt;
   using ssp::st2nt;
   // Device-resident alphas are read through the constant address space (scalar loads, as the
@@ -392,11 +413,18 @@ __global__ __launch_bounds__(kBlock) void k_gemm_outer(const OuterArgs a) {
   const size_t nw = size_t(gridDim.x) * (kBlock / 64);
   const size_t n2 = a.n >> 1, win = 64 * U;
   const double2 z2 = make_double2(0, 0);
-  for (size_t c = gw; c * win < n2; c += nw) {
+  double* nacc = nullptr;  // this thread's accumulators: [j][u] at (j * U + u) * kBlock
+  if constexpr (NRM) {
+    nacc = outer_norm_acc<M>() + threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < M * U; ++q) nacc[q * kBlock] = 0;
+  }
+  // NRM: whole windows only, as ssp::for_windows walks them
+  for (size_t c = gw; NRM ? c < n2 / win : c * win < n2; c += nw) {
     const size_t p0 = c * win + lane;
     bool ok[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) ok[u] = p0 + 64 * u < n2;
+    for (int u = 0; u < U; ++u) ok[u] = NRM || p0 + 64 * u < n2;
     double2 acc[U][M];
 #pragma unroll
     for (int u = 0; u < U; ++u)
@@ -492,6 +520,83 @@ __global__ __launch_bounds__(kBlock) void k_gemm_outer(const OuterArgs a) {
 #pragma unroll
         for (int j = 0; j < M; ++j)
           if (j < a.m) st2nt(a.y[j] + 2 * (p0 + 64 * u), acc[u][j]);
+    if constexpr (NRM) {
+#pragma unroll
+      for (int j = 0; j < M; ++j)
+        if (j < a.m) {
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            double s = nacc[(j * U + u) * kBlock];
+            s = fma(acc[u][j].x, acc[u][j].x, s);
+            s = fma(acc[u][j].y, acc[u][j].y, s);
+            nacc[(j * U + u) * kBlock] = s;
+          }
+          // one destination's accumulators in registers at a time: scheduled freely, all 4 M are loaded
+          // up front (100, 126, 175, 242 VGPRs at M = 1, 2, 4, 8 with the epilogue: a wave per SIMD
+          // fewer than the instances without norms at M = 1 and M = 4)
+          __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+  }
+  if constexpr (NRM) {
+    if (blockIdx.x == 0) {
+      const size_t p = (n2 / win) * win + threadIdx.x;  // fewer than win = kBlock positions are left
+      if (p < n2) {
+        for (int j = 0; j < a.m; ++j) {
+          double2 v = z2;
+          for (int i = 0; i < a.k; ++i) {
+            const double al = alpha(i * a.m + j);
+            const double2 xv = ld2(a.x[i] + 2 * p);
+            v.x = fma(al, xv.x, v.x);
+            v.y = fma(al, xv.y, v.y);
+          }
+          if constexpr (EPI) {
+            if ((a.epi_mask >> j) & 1) {
+              const double2 ev = ld2(a.x[a.k + j] + 2 * p);
+              v.x = fma(a.epi[j], ev.x, v.x);
+              v.y = fma(a.epi[j], ev.y, v.y);
+            }
+          }
+          *reinterpret_cast<double2*>(a.y[j] + 2 * p) = v;
+          double s = nacc[j * U * kBlock];
+          s = fma(v.x, v.x, s);
+          s = fma(v.y, v.y, s);
+          nacc[j * U * kBlock] = s;
+        }
+      }
+      if ((a.n & 1) && threadIdx.x == 0) {
+        const size_t e = a.n - 1;
+        for (int j = 0; j < a.m; ++j) {
+          double v = 0.0;
+          for (int i = 0; i < a.k; ++i) v = fma(alpha(i * a.m + j), a.x[i][e], v);
+          if constexpr (EPI) {
+            if ((a.epi_mask >> j) & 1) v = fma(a.epi[j], a.x[a.k + j][e], v);
+          }
+          a.y[j][e] = v;
+          nacc[j * U * kBlock] = fma(v, v, nacc[j * U * kBlock]);
+        }
+      }
+    }
+    __shared__ double red[kBlock / 64][M];
+#pragma unroll
+    for (int j = 0; j < M; ++j)
+      if (j < a.m) {
+        const double s0 = nacc[(j * U + 0) * kBlock], s1 = nacc[(j * U + 1) * kBlock];
+        const double s2 = nacc[(j * U + 2) * kBlock], s3 = nacc[(j * U + 3) * kBlock];
+        double v = (s0 + s1) + (s2 + s3);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane == 0) red[threadIdx.x >> 6][j] = v;
+      }
+    __syncthreads();
+    if (int(threadIdx.x) < a.m) {
+      double s = 0;  // block_sum256's order
+#pragma unroll
+      for (int w = 0; w < kBlock / 64; ++w) s += red[w][threadIdx.x];
+      ssp::store_partial(a.partial + size_t(blockIdx.x) * a.m + threadIdx.x, s);
+    }
+    ssp::fold_tail<M>(a.partial, a.tail);
+    return;
   }
   if ((a.n & 1) && blockIdx.x == 0 && threadIdx.x < a.m) {
     const size_t e = a.n - 1;
@@ -1330,7 +1435,35 @@ void launch_outer_sc(ssp_ctx* ctx, unsigned grid, const OuterArgs& a) {
     a.set ? launch_outer_t<false, true, SC>(ctx, grid, a) : launch_outer_t<false, false, SC>(ctx, grid, a);
 }
 
+// The norm-carrying instances (NRM): the unscaled write-only form up to 8 destinations, with or without
+// the epilogue.  16 destinations run 2-position windows and would need 128 KiB of LDS: not built.
+constexpr int kOuterNormDst = 8;
+unsigned outer_norm_grid(const ssp_ctx* ctx, size_t n) { return ssp::win_grid(ctx, n, ssp::kDotU, 8); }
+
+template <bool DEV, bool EPI>
+void launch_outer_nrm(ssp_ctx* ctx, unsigned grid, const OuterArgs& a) {
+  if (a.m <= 1)
+    SSP_LAUNCH((k_gemm_outer<1, DEV, true, false, EPI, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
+  else if (a.m <= 2)
+    SSP_LAUNCH((k_gemm_outer<2, DEV, true, false, EPI, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
+  else if (a.m <= 4)
+    SSP_LAUNCH((k_gemm_outer<4, DEV, true, false, EPI, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
+  else
+    SSP_LAUNCH((k_gemm_outer<8, DEV, true, false, EPI, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
+}
+
 int launch_outer(ssp_ctx* ctx, const OuterArgs& a) {
+  if (a.partial) {  // a flushed record launched by the dot of one of its destinations: k_dot_partial's grid
+    if (!a.set || a.scale_dev || a.m > kOuterNormDst || (a.epi_mask && a.k + a.m > ssp::kOuterSrc))
+      return ssp::set_error(SSP_ERR_ARG, "gemm_outer: norms on a launch that cannot carry them");
+    const unsigned grid = outer_norm_grid(ctx, a.n);
+    if (a.epi_mask)
+      a.alpha_dev ? launch_outer_nrm<true, true>(ctx, grid, a) : launch_outer_nrm<false, true>(ctx, grid, a);
+    else
+      a.alpha_dev ? launch_outer_nrm<true, false>(ctx, grid, a) : launch_outer_nrm<false, false>(ctx, grid, a);
+    SSP_TRY_HIP(hipGetLastError());
+    return SSP_OK;
+  }
   // workgroups per CU of the launch: ctx->outer_per_cu (SSP_OUTER_WG_PER_CU at context creation)
   const unsigned grid = ssp::stream_grid(ctx, a.n / 2 + 1, kOuterWin, unsigned(ctx->outer_per_cu));
   if (a.epi_mask) {  // a flushed record with ssp_axpy terms: write-only, unscaled, its epilogue sources in place
@@ -1543,7 +1676,8 @@ namespace {
 // The launch of a flushed record (pending_outer.h): the write-only kernel its call would have launched,
 // or with attached terms its EPI instantiation, under the call's own ledger row; each term adds one
 // source stream to the row's bytes.
-int launch_record(ssp_ctx* ctx, const ssp::PendingOuter::Record& r) {
+// norms: as the NRM instance, whose fold delivers the m sums of squares as `tail` says.
+int launch_record(ssp_ctx* ctx, const ssp::PendingOuter::Record& r, const ssp::FoldTail* norms = nullptr) {
   const int e = r.terms();
   ssp::LedgerScope ls(ctx, r.set ? "gemm_outer_set" : "gemm_outer", 8.0 * r.n * (r.k + r.m + e));
   OuterArgs a{};
@@ -1573,6 +1707,11 @@ int launch_record(ssp_ctx* ctx, const ssp::PendingOuter::Record& r) {
   const int mi = a.m <= 1 ? 1 : a.m <= 2 ? 2 : a.m <= 4 ? 4 : a.m <= 8 ? 8 : 16;
   std::string tag = shape_tag(dev ? "dev" : "arg", mi, a.set, a.k, a.m, false);
   if (e > 0) tag += " epi" + std::to_string(e);
+  if (norms) {
+    a.partial = ctx->partial;
+    a.tail = *norms;
+    tag += " nrm";
+  }
   ls.detail(tag);
   return launch_outer(ctx, a);
 }
@@ -1580,9 +1719,50 @@ int launch_record(ssp_ctx* ctx, const ssp::PendingOuter::Record& r) {
 
 namespace ssp {
 int flush_outer(ssp_ctx* ctx) {
+  ctx->outer_norms.forget();
   if (!ctx->pending_outer.pending()) return SSP_OK;
   int status = SSP_OK;
   ctx->pending_outer.flush([&](const PendingOuter::Record& r) { status = launch_record(ctx, r); });
+  return status;
+}
+
+bool outer_norms_apply(const ssp_ctx* ctx, const double* y, size_t n) {
+  if (!ctx->outer_norms_on || !ctx->pending_outer.pending()) return false;
+  const PendingOuter::Record& r = ctx->pending_outer.record();
+  if (r.m > kOuterNormDst || n != r.n) return false;
+  for (int j = 0; j < r.m; ++j)
+    if (r.y[j] == y) return true;
+  return false;
+}
+
+int launch_outer_norms(ssp_ctx* ctx) {
+  ctx->outer_norms.forget();
+  if (!ctx->pending_outer.pending()) return SSP_OK;
+  const PendingOuter::Record& r = ctx->pending_outer.record();
+  const int m = r.m;
+  const bool ranks = comm_attached(ctx);
+  FoldTail tail{};
+  int status = ensure_partial(ctx, size_t(outer_norm_grid(ctx, r.n)) * m);
+  if (status == SSP_OK) status = fold_begin(ctx, m, &tail);
+  if (status == SSP_OK && ranks) {
+    // rank-local sums: each served dot reduces its own over the ranks, as the dot it replaces does
+    if (!ctx->norms_dev && hipMalloc(reinterpret_cast<void**>(&ctx->norms_dev), kOuterDst * sizeof(double)) != hipSuccess)
+      status = set_error(SSP_ERR_NOMEM, "hipMalloc of the norm staging failed");
+    tail.out = ctx->norms_dev;
+  }
+  if (status != SSP_OK) {  // the record is launched as it always was, and the dot runs by itself
+    const int plain = flush_outer(ctx);
+    return plain != SSP_OK ? plain : status;
+  }
+  ctx->outer_norms.keep(r.y, m, r.n);
+  ctx->pending_outer.flush([&](const PendingOuter::Record& rec) { status = launch_record(ctx, rec, &tail); });
+  if (status == SSP_OK && !ranks) {
+    // one wait for all m sums, before anything else can reuse the host result buffer
+    double v[kOuterDst];
+    status = fold_finish(ctx, tail, v);
+    if (status == SSP_OK) ctx->outer_norms.set_values(v);
+  }
+  if (status != SSP_OK) ctx->outer_norms.forget();
   return status;
 }
 }  // namespace ssp

@@ -36,7 +36,7 @@ __device__ __forceinline__ double sc1(double v, double s) {
 // Window shape: a wave covers kWinU x 64 consecutive double2 (kWinU KiB) of each vector per visit.
 using ssp::kWinMin;
 using ssp::kWinU;
-constexpr int kDotU = 4;
+using ssp::kDotU;
 
 
 // Sum over the 256 threads of a workgroup; result valid in thread 0.  Fixed order.
@@ -456,6 +456,7 @@ int copy_impl(ssp_ctx* ctx, double alpha, double* x, const double* y, size_t n, 
 int axpy_impl(ssp_ctx* ctx, double alpha, const double* x, double xs, double* y, double ys, size_t n,
               const char* what) {
   SSP_CHECK_CTX_KEEP_ALL(ctx);
+  ctx->outer_norms.forget();  // this prologue launches no record: y may be a vector whose norm is kept
   const bool sc = xs != 1.0 || ys != 1.0;
   // Deferred gemm_outer (pending_outer.h): an unscaled axpy onto exactly one destination of the pending
   // record becomes its epilogue term and launches nothing; x is read by that launch, so its pending
@@ -487,7 +488,28 @@ int axpy_impl(ssp_ctx* ctx, double alpha, const double* x, double xs, double* y,
 
 int dot_impl(ssp_ctx* ctx, const double* x, double xs, const double* y, double ys, size_t n, double* out,
              const char* what) {
-  SSP_CHECK_CTX(ctx);
+  SSP_CHECK_CTX_KEEP_ALL(ctx);
+  // Norms from the deferred gemm_outer (outer_norms.h): the unscaled dot of a vector with itself that
+  // finds it as a destination of the pending record launches the record as its norm-carrying instance,
+  // and that dot and the same dot of the record's other destinations are answered from the sums it left
+  // (no launch, no ledger row; the pending zero fills stay pending: none overlaps a destination).
+  // Every other dot takes the default prologue, which forgets the sums.
+  if (out && x == y && xs == 1.0 && ys == 1.0) {
+    if (ssp::outer_norms_apply(ctx, y, n)) SSP_TRY(ssp::launch_outer_norms(ctx));
+    const int j = ctx->outer_norms.find(y, n);
+    if (j >= 0) {
+      if (!ssp::comm_attached(ctx)) {
+        *out = ctx->outer_norms.value(j);
+        return SSP_OK;
+      }
+      SSP_TRY(ssp::comm_check(ctx));
+      SSP_TRY(ssp::ensure_result(ctx, 1));
+      SSP_TRY_HIP(hipMemcpyAsync(ctx->result_dev, ctx->norms_dev + j, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+      return ssp::reduce_fetch(ctx, out, 1);
+    }
+  }
+  SSP_TRY(ssp::flush_outer(ctx));
+  SSP_TRY(ssp::flush_fills(ctx));
   if (!out) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null out");
   SSP_TRY(check_vec(x, n, what));
   SSP_TRY(check_vec(y, n, what));

@@ -14,6 +14,7 @@
 
 #include "pending_fill.h"
 #include "pending_outer.h"
+#include "outer_norms.h"
 #include "subspace_hip.h"
 
 // Per-operation ledger: HIP events bracket each hot-path kernel on the context's stream, with the
@@ -62,6 +63,14 @@ struct ssp_ctx {
   // same-build A/B, and the eager side of tests/test_deferred_outer_gpu.py).
   bool defer_outer = true;
   ssp::PendingOuter pending_outer;
+  // The norms of the destinations of the last launched record, when the ssp_dot(y, y) of one of them
+  // launched it (outer_norms.h): the NRM instance of k_gemm_outer summed them, and the dots of the other
+  // destinations are answered from here.  SSP_OUTER_NORMS=0: off, every dot runs k_dot_partial (the
+  // same-build A/B, and the switch case of tests/test_outer_norms_gpu.py).  norms_dev: the rank-local
+  // sums when a rank transport is attached (each served dot reduces its own over the ranks).
+  bool outer_norms_on = true;
+  ssp::OuterNorms outer_norms;
+  double* norms_dev = nullptr;
   hipStream_t stream = nullptr;
 
   // HBM arena: freed blocks are kept by rounded size and recycled (Q vectors are created and
@@ -153,6 +162,8 @@ constexpr int kSelectTile = 2048;  // candidates sorted per workgroup in select
 // kWinU x 64 consecutive double2 (kWinU KiB) of each vector per visit.
 constexpr int kWinU = 8;
 constexpr size_t kWinMin = size_t(1) << 24;  // elementwise ops switch to windows from 128 MiB vectors
+// Window of k_dot_partial (KiB per vector per wave visit), and so of the norm-carrying k_gemm_outer.
+constexpr int kDotU = 4;
 
 int set_error(int code, const std::string& msg);
 int hip_error(hipError_t e, const char* what);
@@ -168,7 +179,15 @@ int flush_fills_over(ssp_ctx* ctx, const void* p, size_t n);
 int overwrite_fills(ssp_ctx* ctx, const void* p, size_t n);
 // Deferred gemm_outer (kernels_panel.hip): launches the context's pending record, if there is one, under
 // its "gemm_outer" / "gemm_outer_set" ledger row.
+// It also forgets the kept norms (outer_norms.h): every entry point but ssp_dot comes through here or
+// forgets them itself (ssp_axpy).
 int flush_outer(ssp_ctx* ctx);
+// The ssp_dot(y, y, n) that finds a pending record: true when y is exactly one of its destinations, n its
+// length and the norm-carrying instance exists for its width.  launch_outer_norms then launches the
+// record as that instance and keeps the m sums in ctx->outer_norms (one rank: their values, after one
+// wait; ranks: the rank-local sums in ctx->norms_dev).
+bool outer_norms_apply(const ssp_ctx* ctx, const double* y, size_t n);
+int launch_outer_norms(ssp_ctx* ctx);
 // use_device, then flush_outer and flush_fills.
 int enter(ssp_ctx* ctx);
 int ensure_partial(ssp_ctx* ctx, size_t n_doubles);
