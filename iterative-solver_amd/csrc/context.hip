@@ -58,6 +58,31 @@ int enter(ssp_ctx* ctx) {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+int check_vec(const void* p, size_t n, const char* what) {
+  if (n == 0) return SSP_OK;
+  if (!p) return set_error(SSP_ERR_ARG, std::string(what) + ": null vector");
+  if (!aligned16(p)) return set_error(SSP_ERR_ARG, std::string(what) + ": vector not 16-byte aligned");
+  return SSP_OK;
+}
+
+int check_ptrs(const void* const* v, int count, size_t n, const char* what) {
+  if (count > 0 && !v) return set_error(SSP_ERR_ARG, std::string(what) + ": null vector list");
+  for (int i = 0; i < count; ++i) SSP_TRY(check_vec(v[i], n, what));
+  return SSP_OK;
+}
+
+std::string shape_tag(const char* kind, int a, int b, int c, int d, bool sc) {
+  char t[96];
+  std::snprintf(t, sizeof(t), "%s<%d,%d> %dx%d%s", kind, a, b, c, d, sc ? " sc" : "");
+  return t;
+}
+
+bool any_scaled(const double* s, int n) {
+  for (int i = 0; s && i < n; ++i)
+    if (s[i] != 1.0) return true;
+  return false;
+}
+
 unsigned stream_grid(const ssp_ctx* ctx, size_t work_items, unsigned per_thread, unsigned blocks_per_cu) {
   const size_t per_block = size_t(kBlock) * per_thread;
   size_t blocks = (work_items + per_block - 1) / per_block;
@@ -483,8 +508,8 @@ int ssp_ctx_create(int device, ssp_ctx** out) {
   }
   if (const char* sm = std::getenv("SSP_SYNTH_MERGE")) ctx->synth_merge = std::atoi(sm) != 0;
   if (const char* df = std::getenv("SSP_DEFER_FILL")) ctx->defer_fill = std::atoi(df) != 0;
-  if (const char* dout = std::getenv("SSP_DEFER_OUTER")) ctx->defer_outer = std::atoi(dout) != 0;
-  if (const char* on = std::getenv("SSP_OUTER_NORMS")) ctx->outer_norms_on = std::atoi(on) != 0;
+  if (const char* dout = std::getenv("SSP_DEFER_OUTER")) ctx->outer.defer = std::atoi(dout) != 0;
+  if (const char* on = std::getenv("SSP_OUTER_NORMS")) ctx->outer.norms_on = std::atoi(on) != 0;
   if (const char* ct = std::getenv("SSP_COMM_TIMEOUT_S")) {
     const double v = std::atof(ct);
     if (v > 0) ctx->comm_timeout_s = v;
@@ -513,7 +538,7 @@ int ssp_ctx_destroy(ssp_ctx* ctx) {
   if (!ctx) return SSP_OK;
   (void)hipSetDevice(ctx->device);
   ctx->pending_fills.clear();  // nobody can read the vectors of a destroyed context
-  ctx->pending_outer.discard();
+  ctx->outer.pending.discard();
   (void)ssp::p2p_detach(ctx);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->comm) ncclCommDestroy(ctx->comm);
@@ -527,7 +552,7 @@ int ssp_ctx_destroy(ssp_ctx* ctx) {
   for (auto& b : ctx->free_blocks) (void)hipFree(b.second);
   for (auto& b : ctx->live_blocks) (void)hipFree(b.first);
   if (ctx->partial) (void)hipFree(ctx->partial);
-  if (ctx->norms_dev) (void)hipFree(ctx->norms_dev);
+  if (ctx->outer.norms_dev) (void)hipFree(ctx->outer.norms_dev);
   if (ctx->result_dev) (void)hipFree(ctx->result_dev);
   if (ctx->result_host) (void)hipHostFree(ctx->result_host);
   if (ctx->pub_flag) (void)hipHostFree(ctx->pub_flag);

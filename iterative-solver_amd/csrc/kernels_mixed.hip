@@ -579,19 +579,6 @@ __global__ __launch_bounds__(kBlock) void k_mx_inner(const MxInnerArgs a) {
 bool bad_dtype(ssp_dtype t) { return t != SSP_F64 && t != SSP_F32; }
 double esize(ssp_dtype t) { return t == SSP_F32 ? 4.0 : 8.0; }
 
-int check_vec(const void* p, size_t n, const char* what) {
-  if (n == 0) return SSP_OK;
-  if (!p) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null vector");
-  if (!ssp::aligned16(p)) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": vector not 16-byte aligned");
-  return SSP_OK;
-}
-
-int check_ptrs(const void* const* v, int count, size_t n, const char* what) {
-  if (count > 0 && !v) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null vector list");
-  for (int i = 0; i < count; ++i) SSP_TRY(check_vec(v[i], n, what));
-  return SSP_OK;
-}
-
 // The storage pair of a mixed call as types: launch(X, Y) gets a value of the first operand's storage type
 // and one of the second's (tags: only decltype(X), decltype(Y) are used) and launches the kernels of that
 // pair.  (f64, f64) never reaches here: every entry point forwards it to its f64 call.
@@ -810,8 +797,8 @@ int ssp_q32_gemm_inner_cols(ssp_ctx* ctx, const double* const* xx, const double*
   }
   if (m * k > 0 && !out) return ssp::set_error(SSP_ERR_ARG, "ssp_q32_gemm_inner_cols: null out");
   if (m == 0 || k == 0) return SSP_OK;
-  SSP_TRY(check_ptrs(reinterpret_cast<const void* const*>(xx), m, n, "ssp_q32_gemm_inner_cols"));
-  SSP_TRY(check_ptrs(yy, k, n, "ssp_q32_gemm_inner_cols"));
+  SSP_TRY(ssp::check_ptrs(xx, m, n, "ssp_q32_gemm_inner_cols"));
+  SSP_TRY(ssp::check_ptrs(yy, k, n, "ssp_q32_gemm_inner_cols"));
   if (n32 == 0)
     return ssp_gemm_inner_scaled(ctx, xx, xs, m, reinterpret_cast<const double* const*>(yy), ys, k, n, out);
   if (n32 == k)  // (its n = 0 is the f64 entry's, in the same m x k layout as its other paths)
@@ -892,9 +879,9 @@ int ssp_q32_combine_widen(ssp_ctx* ctx, const double* alphas, const float* const
                           double* const* ww, int m, size_t n) {
   SSP_CHECK_CTX_KEEP_FILLS(ctx);
   if (m < 0 || k < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_q32_combine_widen: negative dimension");
-  SSP_TRY(check_ptrs(reinterpret_cast<const void* const*>(xx), k, n, "ssp_q32_combine_widen"));
-  SSP_TRY(check_ptrs(reinterpret_cast<const void* const*>(yy), m, n, "ssp_q32_combine_widen"));
-  SSP_TRY(check_ptrs(reinterpret_cast<const void* const*>(ww), m, n, "ssp_q32_combine_widen"));
+  SSP_TRY(ssp::check_ptrs(xx, k, n, "ssp_q32_combine_widen"));
+  SSP_TRY(ssp::check_ptrs(yy, m, n, "ssp_q32_combine_widen"));
+  SSP_TRY(ssp::check_ptrs(ww, m, n, "ssp_q32_combine_widen"));
   if (m == 0 || n == 0) return SSP_OK;
   if (k > 0 && !alphas) return ssp::set_error(SSP_ERR_ARG, "ssp_q32_combine_widen: null alphas");
   for (int j = 0; j < m; ++j) {
@@ -970,7 +957,7 @@ int ssp_download_f32(ssp_ctx* ctx, float* dst, const float* src, size_t n) {
 
 int ssp_fill_f32(ssp_ctx* ctx, double alpha, float* x, size_t n) {
   SSP_CHECK_CTX(ctx);
-  SSP_TRY(check_vec(x, n, "ssp_fill_f32"));
+  SSP_TRY(ssp::check_vec(x, n, "ssp_fill_f32"));
   if (n == 0) return SSP_OK;
   ssp::LedgerScope ls(ctx, "fill_f32", 4.0 * n);
   SSP_LAUNCH(k_mx_fill, dim3(ssp::stream_grid(ctx, n / 4 + 1, 1, 64)), dim3(kBlock), 0, ctx->stream, x, n, alpha);
@@ -980,7 +967,7 @@ int ssp_fill_f32(ssp_ctx* ctx, double alpha, float* x, size_t n) {
 
 int ssp_scal_f32(ssp_ctx* ctx, double alpha, float* x, size_t n) {
   SSP_CHECK_CTX(ctx);
-  SSP_TRY(check_vec(x, n, "ssp_scal_f32"));
+  SSP_TRY(ssp::check_vec(x, n, "ssp_scal_f32"));
   if (n == 0) return SSP_OK;
   ssp::LedgerScope ls(ctx, "scal_f32", 8.0 * n);
   SSP_LAUNCH(k_mx_scal, dim3(quad_grid(ctx, n, kMxU, 16)), dim3(kBlock), 0, ctx->stream, x, n, alpha);
@@ -991,8 +978,8 @@ int ssp_scal_f32(ssp_ctx* ctx, double alpha, float* x, size_t n) {
 int ssp_mx_copy(ssp_ctx* ctx, void* x, ssp_dtype tx, const void* y, ssp_dtype ty, double ys, size_t n) {
   SSP_CHECK_CTX(ctx);
   if (bad_dtype(tx) || bad_dtype(ty)) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_copy: bad dtype");
-  SSP_TRY(check_vec(x, n, "ssp_mx_copy"));
-  SSP_TRY(check_vec(y, n, "ssp_mx_copy"));
+  SSP_TRY(ssp::check_vec(x, n, "ssp_mx_copy"));
+  SSP_TRY(ssp::check_vec(y, n, "ssp_mx_copy"));
   if (tx == SSP_F64 && ty == SSP_F64) {
     double* xd = static_cast<double*>(x);
     const double* yd = static_cast<const double*>(y);
@@ -1011,7 +998,7 @@ int ssp_quantise_f32(ssp_ctx* ctx, double* const* xx, const double* xs, int m, s
   SSP_CHECK_CTX(ctx);  // pending zero fills are stored: every vector is read
   if (m < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_quantise_f32: negative dimension");
   if (m == 0 || n == 0) return SSP_OK;
-  SSP_TRY(check_ptrs(reinterpret_cast<const void* const*>(xx), m, n, "ssp_quantise_f32"));
+  SSP_TRY(ssp::check_ptrs(xx, m, n, "ssp_quantise_f32"));
   ssp::LedgerScope ls(ctx, "quantise_f32", 16.0 * m * n);
   for (int v0 = 0; v0 < m; v0 += ssp::kPrecVec) {
     QuantArgs a{};
@@ -1030,8 +1017,8 @@ int ssp_quantise_f32(ssp_ctx* ctx, double* const* xx, const double* xs, int m, s
 int ssp_mx_axpy(ssp_ctx* ctx, double alpha, const void* x, ssp_dtype tx, void* y, ssp_dtype ty, size_t n) {
   SSP_CHECK_CTX(ctx);
   if (bad_dtype(tx) || bad_dtype(ty)) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_axpy: bad dtype");
-  SSP_TRY(check_vec(x, n, "ssp_mx_axpy"));
-  SSP_TRY(check_vec(y, n, "ssp_mx_axpy"));
+  SSP_TRY(ssp::check_vec(x, n, "ssp_mx_axpy"));
+  SSP_TRY(ssp::check_vec(y, n, "ssp_mx_axpy"));
   if (tx == SSP_F64 && ty == SSP_F64) return ssp_axpy(ctx, alpha, static_cast<const double*>(x), static_cast<double*>(y), n);
   if (n == 0) return SSP_OK;
   if (ssp::exact_mode(ctx, n)) {
@@ -1058,8 +1045,8 @@ int ssp_mx_dot(ssp_ctx* ctx, const void* x, ssp_dtype tx, const void* y, ssp_dty
   SSP_CHECK_CTX(ctx);
   if (bad_dtype(tx) || bad_dtype(ty)) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_dot: bad dtype");
   if (!out) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_dot: null out");
-  SSP_TRY(check_vec(x, n, "ssp_mx_dot"));
-  SSP_TRY(check_vec(y, n, "ssp_mx_dot"));
+  SSP_TRY(ssp::check_vec(x, n, "ssp_mx_dot"));
+  SSP_TRY(ssp::check_vec(y, n, "ssp_mx_dot"));
   if ((tx == SSP_F64 && ty == SSP_F64) || n == 0)  // n = 0: the f64 entry's zero, reduced over ranks
     return ssp_dot(ctx, static_cast<const double*>(x), static_cast<const double*>(y), n, out);
   if (ssp::exact_mode(ctx, n)) {
@@ -1093,8 +1080,8 @@ int ssp_mx_rhs_residual_norms(ssp_ctx* ctx, const void* const* bb, ssp_dtype tb,
   if (m < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_rhs_residual_norms: negative dimension");
   if (m == 0) return SSP_OK;
   if (!s || !out) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_rhs_residual_norms: null scales or out");
-  SSP_TRY(check_ptrs(bb, m, n, "ssp_mx_rhs_residual_norms"));
-  SSP_TRY(check_ptrs(reinterpret_cast<const void* const*>(yy), m, n, "ssp_mx_rhs_residual_norms"));
+  SSP_TRY(ssp::check_ptrs(bb, m, n, "ssp_mx_rhs_residual_norms"));
+  SSP_TRY(ssp::check_ptrs(yy, m, n, "ssp_mx_rhs_residual_norms"));
   for (int j = 0; n > 0 && j < m; ++j)
     for (int i = 0; i < m; ++i)
       if (static_cast<const void*>(yy[j]) == bb[i] || (i < j && yy[i] == yy[j]))
@@ -1160,8 +1147,8 @@ int ssp_mx_gemm_inner(ssp_ctx* ctx, const void* const* xx, ssp_dtype tx, const d
   if (m < 0 || k < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_gemm_inner: negative dimension");
   if (m * k > 0 && !out) return ssp::set_error(SSP_ERR_ARG, "ssp_mx_gemm_inner: null out");
   if (m == 0 || k == 0) return SSP_OK;
-  SSP_TRY(check_ptrs(xx, m, n, "ssp_mx_gemm_inner"));
-  SSP_TRY(check_ptrs(yy, k, n, "ssp_mx_gemm_inner"));
+  SSP_TRY(ssp::check_ptrs(xx, m, n, "ssp_mx_gemm_inner"));
+  SSP_TRY(ssp::check_ptrs(yy, k, n, "ssp_mx_gemm_inner"));
   if ((tx == SSP_F64 && ty == SSP_F64) || n == 0)  // n = 0: the f64 entry's zeros, reduced over ranks
     return ssp_gemm_inner_scaled(ctx, reinterpret_cast<const double* const*>(xx), xs, m,
                                  reinterpret_cast<const double* const*>(yy), ys, k, n, out);
@@ -1229,8 +1216,8 @@ int ssp_mx_gemm_outer(ssp_ctx* ctx, const double* alphas, const void* const* xx,
     return set ? ssp_gemm_outer_set_scaled(ctx, alphas, xd, xs, k, yd, m, n)
                : ssp_gemm_outer_scaled(ctx, alphas, xd, xs, k, yd, nullptr, m, n);
   }
-  SSP_TRY(check_ptrs(xx, k, n, "ssp_mx_gemm_outer"));
-  SSP_TRY(check_ptrs(const_cast<const void* const*>(yy), m, n, "ssp_mx_gemm_outer"));
+  SSP_TRY(ssp::check_ptrs(xx, k, n, "ssp_mx_gemm_outer"));
+  SSP_TRY(ssp::check_ptrs(yy, m, n, "ssp_mx_gemm_outer"));
   if (m == 0 || n == 0) return SSP_OK;
   if (k == 0) {
     for (int j = 0; set && j < m; ++j) {

@@ -1,9 +1,10 @@
-// Tall-skinny panel kernels: gemm_inner (m x k overlaps) and gemm_outer (k sources -> m destinations).
+// Tall-skinny panel kernels: gemm_inner (m x k overlaps), the fused panel passes (MGS steps, the block
+// transform) and precondition_norms.  gemm_outer (k sources -> m destinations) is kernels_outer.hip.
 //
-// Reference: util/gemm.h:257-279 computes both pairwise (handler.dot / handler.axpy per pair), so a
-// 8 x 48 gemm_inner streams 2*8*48 vectors and a 48 -> 8 gemm_outer streams 3*8*48 vectors.  Here
-// every vector of the panel is read from HBM exactly once per call:
-//   gemm_inner  bytes = 8 N (m + k)       gemm_outer  bytes = 8 N (k + 2 m)
+// Reference: util/gemm.h:257-279 computes the overlaps pairwise (handler.dot per pair), so a 8 x 48
+// gemm_inner streams 2*8*48 vectors.  Here every vector of the panel is read from HBM exactly once per
+// call:
+//   gemm_inner  bytes = 8 N (m + k)
 //
 // gemm_inner runs on the f64 matrix cores with the 4-block v_mfma_f64_4x4x4_f64 (measured lane map,
 // tools/mfma_probe.hip):  lane l = 16k + 4b + i holds A_b[i][k] and B_b[k][i];  C_b[i][j] sits in
@@ -17,7 +18,6 @@
 // through LDS, workgroups by a fixed-order second pass (ssp::launch_reduce_partials): bitwise
 // reproducible, and identical on every rank after the RCCL allreduce.
 #include <algorithm>
-#include <cstdio>
 #include <cstddef>
 #include <cstdlib>
 #include <vector>
@@ -27,17 +27,7 @@
 namespace {
 
 using ssp::kBlock;
-
-__device__ __forceinline__ double2 ld2(const double* p) { return *reinterpret_cast<const double2*>(p); }
-// Deferred scal (include/subspace_hip.h *_scaled): v * s is the one rounding an eager scal stores.
-template <bool SC>
-__device__ __forceinline__ double2 sc2(double2 v, double s) {
-  return SC ? make_double2(v.x * s, v.y * s) : v;
-}
-template <bool SC>
-__device__ __forceinline__ double sc1(double v, double s) {
-  return SC ? v * s : v;
-}
+using ssp::ld2, ssp::sc1, ssp::sc2;
 
 struct InnerArgs {
   const double* x[ssp::kInnerRows];  // rows: MG groups of 4
@@ -338,276 +328,6 @@ __global__ __launch_bounds__(kBlock) void k_gemm_inner_row_win(const InnerArgs a
     ssp::store_partial(a.partial + size_t(blockIdx.x) * K + threadIdx.x, v);
   }
   if (a.tail.counter) ssp::fold_tail<K>(a.partial, a.tail);
-}
-
-struct OuterArgs {
-  const double* x[ssp::kOuterSrc];
-  double* y[ssp::kOuterDst];
-  int k;
-  int m;
-  int set;  // 1: yy[j] = sum (destinations not read: fill(0) + gemm_outer in one pass)
-  // EPI: bit j set: y[j] += epi[j] * x[k + j] (the epilogue sources ride in the source slots past the
-  // k sources, so k + m <= kOuterSrc).  The new members sit in the padding after `set` and behind
-  // `alpha`: every other member keeps its offset, and the instances without EPI their code.
-  int epi_mask;
-  size_t n;
-  const double* alpha_dev;         // k*m > kOuterAlpha: alpha[i*m + j] in device memory
-  const double* scale_dev;         // SC: deferred scales, sources [0, k) then destinations [k, k + m)
-  double alpha[ssp::kOuterAlpha];  // alpha[i*m + j] in the argument block
-  double epi[ssp::kOuterDst];
-  // NRM: per-workgroup sums of squares partial[b * m + j], folded by `tail` (nout = m).  At the end of
-  // the block, for the same reason.
-  double* partial;
-  ssp::FoldTail tail;
-};
-static_assert(sizeof(OuterArgs) <= 4000, "kernel argument block too large");
-static_assert(ssp::PendingOuter::kSrc == ssp::kOuterSrc && ssp::PendingOuter::kDst == ssp::kOuterDst,
-              "pending_outer.h records one launch");
-
-// yy[j] += sum_i alpha(i,j) xx[i]: for each destination the sources are added in order i = 0..k-1,
-// as the reference's pairwise axpy loop does (util/gemm.h:259-264).  Each wave owns windows of
-// kOuterWin consecutive double2 positions (64 lanes x 16 B x kOuterWin contiguous bytes per vector)
-// and loads 4 sources x kOuterWin positions before the fmas; sources and destinations are streamed
-// once, with nontemporal accesses (tools/mb_stream.hip: 5.35 TB/s against 4.8 for one position per
-// lane and plain accesses).
-constexpr int kOuterWin = 4;
-static_assert(kOuterWin == ssp::kDotU, "the norm-carrying instance walks k_dot_partial's windows");
-
-// SET (a.set = 1) is a separate instantiation: the write-only construct_solution form shows under its
-// own name in rocprofv3 statistics, so its launches are not averaged with the read-modify-write ones.
-// SC: sources and (read-modify-write) destinations with deferred scales, applied as each element is
-// loaded (include/subspace_hip.h ssp_gemm_outer_scaled).
-// EPI (the flushed record of pending_outer.h with attached ssp_axpy terms): before destination j of
-// a.epi_mask is stored, epi[j] * x[k + j] is added to its finished sum by the fma k_axpy_win would have
-// done on the stored value.  Unmasked destinations take no term: fma(0, x, acc) would turn a -0.0 sum
-// into +0.0 and an infinite x into NaN.
-// NRM (the record launched by the ssp_dot(y, y) of one of its destinations, outer_norms.h): next to the
-// stores, the sum of squares of every destination as stored, in the bits k_dot_partial<true, false> and
-// its fold give on the stored vector.  The launch takes that kernel's grid and its walk: whole windows in
-// the window loop (window position u into accumulator u: fma(v.x, v.x, .), fma(v.y, v.y, .)), then the
-// positions past the last whole window one per thread of workgroup 0 and the odd last element in its
-// thread 0, both into accumulator 0; (s0 + s1) + (s2 + s3), block_sum256's tree, partial[b * m + j],
-// ssp::fold_tail.  The stored elements do not depend on the thread that forms them.  The 4 M
-// accumulators per lane live in LDS ([j][u][thread]: every lane its own bank pair, 8 M KiB per
-// workgroup), not in 8 M more VGPRs, which would halve the M = 8 instance's waves per SIMD.
-template <int M>
-__device__ __forceinline__ double* outer_norm_acc() {
-  __shared__ double acc[M * kOuterWin * kBlock];
-  return acc;
-}
-
-template <int M, bool DEV, bool SET, bool SC = false, bool EPI = false, bool NRM = false>
-__global__ __launch_bounds__(kBlock) void k_gemm_outer(const OuterArgs a) {
-  static_assert(!EPI || (SET && !SC), "the epilogue rides on the unscaled write-only form");
-  static_assert(!NRM || (SET && !SC && M <= 8), "the norms ride on the unscaled write-only form, 4-position windows");
-  using ssp::ld2nt;
-  using ssp::st2nt;
-  // Device-resident alphas are read through the constant address space (scalar loads, as the
-  // argument block's are): they are uniform across the wave and read-only in the kernel.
-  using cdouble = const __attribute__((address_space(4))) double;
-  const auto alpha = [&](int idx) { return DEV ? ((cdouble*)a.alpha_dev)[idx] : a.alpha[idx]; };
-  const auto scale = [&](int idx) { return SC ? ((cdouble*)a.scale_dev)[idx] : 1.0; };
-  constexpr int U = M > 8 ? 2 : kOuterWin;  // 16 destinations: 2 windows keep 2 waves per SIMD
-  const int lane = threadIdx.x & 63;
-  const size_t gw = size_t(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
-  const size_t nw = size_t(gridDim.x) * (kBlock / 64);
-  const size_t n2 = a.n >> 1, win = 64 * U;
-  const double2 z2 = make_double2(0, 0);
-  double* nacc = nullptr;  // this thread's accumulators: [j][u] at (j * U + u) * kBlock
-  if constexpr (NRM) {
-    nacc = outer_norm_acc<M>() + threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < M * U; ++q) nacc[q * kBlock] = 0;
-  }
-  // NRM: whole windows only, as ssp::for_windows walks them
-  for (size_t c = gw; NRM ? c < n2 / win : c * win < n2; c += nw) {
-    const size_t p0 = c * win + lane;
-    bool ok[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) ok[u] = NRM || p0 + 64 * u < n2;
-    double2 acc[U][M];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-#pragma unroll
-      for (int j = 0; j < M; ++j) acc[u][j] = (j < a.m && ok[u] && !SET) ? ld2nt(a.y[j] + 2 * (p0 + 64 * u)) : z2;
-    if constexpr (SC && !SET) {
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int j = 0; j < M; ++j)
-          if (j < a.m) acc[u][j] = sc2<SC>(acc[u][j], scale(a.k + j));  // only a.k + a.m scales exist
-    }
-    int i = 0;
-    for (; i + 4 <= a.k; i += 4) {
-      double2 xv[4][U];
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int u = 0; u < U; ++u) xv[b][u] = ok[u] ? ld2nt(a.x[i + b] + 2 * (p0 + 64 * u)) : z2;
-      if constexpr (SC) {
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-          for (int u = 0; u < U; ++u) xv[b][u] = sc2<SC>(xv[b][u], scale(i + b));
-      }
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-#pragma unroll
-        for (int j = 0; j < M; ++j) {
-          if (j < a.m) {
-            const double al = alpha((i + b) * a.m + j);
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-              acc[u][j].x = fma(al, xv[b][u].x, acc[u][j].x);
-              acc[u][j].y = fma(al, xv[b][u].y, acc[u][j].y);
-            }
-          }
-        }
-    }
-    for (; i < a.k; ++i) {
-      double2 xv[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) xv[u] = ok[u] ? ld2nt(a.x[i] + 2 * (p0 + 64 * u)) : z2;
-      if constexpr (SC) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) xv[u] = sc2<SC>(xv[u], scale(i));
-      }
-#pragma unroll
-      for (int j = 0; j < M; ++j) {
-        if (j < a.m) {
-          const double al = alpha(i * a.m + j);
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            acc[u][j].x = fma(al, xv[u].x, acc[u][j].x);
-            acc[u][j].y = fma(al, xv[u].y, acc[u][j].y);
-          }
-        }
-      }
-    }
-    if constexpr (EPI) {
-      // B destinations' terms in flight.  The compiler gives ev registers of its own beside xv's (16 B
-      // VGPRs at U = 4), so B is what keeps each instance at the waves per SIMD of its write-only form:
-      // two at M = 8 (234 VGPRs, two waves, 8 loads per lane in flight), one elsewhere.
-      constexpr int B = M == 8 ? 2 : 1;
-#pragma unroll
-      for (int j0 = 0; j0 < M; j0 += B) {
-        double2 ev[B][U];
-        bool on[B];
-#pragma unroll
-        for (int b = 0; b < B; ++b) {
-          on[b] = j0 + b < a.m && ((a.epi_mask >> (j0 + b)) & 1);
-          if (on[b]) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) ev[b][u] = ok[u] ? ld2nt(a.x[a.k + j0 + b] + 2 * (p0 + 64 * u)) : z2;
-          }
-        }
-#pragma unroll
-        for (int b = 0; b < B; ++b) {
-          if (on[b]) {
-            const double ea = a.epi[j0 + b];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-              acc[u][j0 + b].x = fma(ea, ev[b][u].x, acc[u][j0 + b].x);
-              acc[u][j0 + b].y = fma(ea, ev[b][u].y, acc[u][j0 + b].y);
-            }
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (ok[u])
-#pragma unroll
-        for (int j = 0; j < M; ++j)
-          if (j < a.m) st2nt(a.y[j] + 2 * (p0 + 64 * u), acc[u][j]);
-    if constexpr (NRM) {
-#pragma unroll
-      for (int j = 0; j < M; ++j)
-        if (j < a.m) {
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            double s = nacc[(j * U + u) * kBlock];
-            s = fma(acc[u][j].x, acc[u][j].x, s);
-            s = fma(acc[u][j].y, acc[u][j].y, s);
-            nacc[(j * U + u) * kBlock] = s;
-          }
-          // one destination's accumulators in registers at a time: scheduled freely, all 4 M are loaded
-          // up front (100, 126, 175, 242 VGPRs at M = 1, 2, 4, 8 with the epilogue: a wave per SIMD
-          // fewer than the instances without norms at M = 1 and M = 4)
-          __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-  }
-  if constexpr (NRM) {
-    if (blockIdx.x == 0) {
-      const size_t p = (n2 / win) * win + threadIdx.x;  // fewer than win = kBlock positions are left
-      if (p < n2) {
-        for (int j = 0; j < a.m; ++j) {
-          double2 v = z2;
-          for (int i = 0; i < a.k; ++i) {
-            const double al = alpha(i * a.m + j);
-            const double2 xv = ld2(a.x[i] + 2 * p);
-            v.x = fma(al, xv.x, v.x);
-            v.y = fma(al, xv.y, v.y);
-          }
-          if constexpr (EPI) {
-            if ((a.epi_mask >> j) & 1) {
-              const double2 ev = ld2(a.x[a.k + j] + 2 * p);
-              v.x = fma(a.epi[j], ev.x, v.x);
-              v.y = fma(a.epi[j], ev.y, v.y);
-            }
-          }
-          *reinterpret_cast<double2*>(a.y[j] + 2 * p) = v;
-          double s = nacc[j * U * kBlock];
-          s = fma(v.x, v.x, s);
-          s = fma(v.y, v.y, s);
-          nacc[j * U * kBlock] = s;
-        }
-      }
-      if ((a.n & 1) && threadIdx.x == 0) {
-        const size_t e = a.n - 1;
-        for (int j = 0; j < a.m; ++j) {
-          double v = 0.0;
-          for (int i = 0; i < a.k; ++i) v = fma(alpha(i * a.m + j), a.x[i][e], v);
-          if constexpr (EPI) {
-            if ((a.epi_mask >> j) & 1) v = fma(a.epi[j], a.x[a.k + j][e], v);
-          }
-          a.y[j][e] = v;
-          nacc[j * U * kBlock] = fma(v, v, nacc[j * U * kBlock]);
-        }
-      }
-    }
-    __shared__ double red[kBlock / 64][M];
-#pragma unroll
-    for (int j = 0; j < M; ++j)
-      if (j < a.m) {
-        const double s0 = nacc[(j * U + 0) * kBlock], s1 = nacc[(j * U + 1) * kBlock];
-        const double s2 = nacc[(j * U + 2) * kBlock], s3 = nacc[(j * U + 3) * kBlock];
-        double v = (s0 + s1) + (s2 + s3);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane == 0) red[threadIdx.x >> 6][j] = v;
-      }
-    __syncthreads();
-    if (int(threadIdx.x) < a.m) {
-      double s = 0;  // block_sum256's order
-#pragma unroll
-      for (int w = 0; w < kBlock / 64; ++w) s += red[w][threadIdx.x];
-      ssp::store_partial(a.partial + size_t(blockIdx.x) * a.m + threadIdx.x, s);
-    }
-    ssp::fold_tail<M>(a.partial, a.tail);
-    return;
-  }
-  if ((a.n & 1) && blockIdx.x == 0 && threadIdx.x < a.m) {
-    const size_t e = a.n - 1;
-    const int j = threadIdx.x;
-    double v = SET ? 0.0 : sc1<SC>(a.y[j][e], scale(a.k + j));
-    for (int i = 0; i < a.k; ++i) v = fma(alpha(i * a.m + j), sc1<SC>(a.x[i][e], scale(i)), v);
-    if constexpr (EPI) {
-      if ((a.epi_mask >> j) & 1) v = fma(a.epi[j], a.x[a.k + j][e], v);
-    }
-    a.y[j][e] = v;
-  }
 }
 
 // Fused MGS step: y_j += c_j x (the same fma as a one-source gemm_outer),
@@ -1294,16 +1014,6 @@ __global__ __launch_bounds__(kBlock) void k_axpy_pairs_norm(const AxpyPairsArgs 
   if (a.tail.counter) ssp::fold_tail<(M < 8 ? M : 8)>(a.partial, a.tail);
 }
 
-int check_ptrs(const double* const* v, int count, size_t n, const char* what) {
-  if (count > 0 && !v) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null vector list");
-  if (n == 0) return SSP_OK;
-  for (int i = 0; i < count; ++i) {
-    if (!v[i]) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null vector");
-    if (!ssp::aligned16(v[i])) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": vector not 16-byte aligned");
-  }
-  return SSP_OK;
-}
-
 // Column groups per launch for MG row groups (accumulator registers: MG * NG doubles per lane):
 // 16 (64 columns, the launch maximum) for every row-group count, so one launch reads every vector
 // once (tools/mb_inner.hip: 16 x 64 at 5.9 TB/s in one launch against 4.3 TB/s in three).
@@ -1413,85 +1123,8 @@ int launch_inner(ssp_ctx* ctx, const InnerArgs& a, unsigned grid, bool sc, bool 
   return sc ? launch_inner_sc<true>(ctx, a, grid, pre) : launch_inner_sc<false>(ctx, a, grid, pre);
 }
 
-template <bool DEV, bool SET, bool SC, bool EPI = false>
-void launch_outer_t(ssp_ctx* ctx, unsigned grid, const OuterArgs& a) {
-  if (a.m <= 1)
-    SSP_LAUNCH((k_gemm_outer<1, DEV, SET, SC, EPI>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
-  else if (a.m <= 2)
-    SSP_LAUNCH((k_gemm_outer<2, DEV, SET, SC, EPI>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
-  else if (a.m <= 4)
-    SSP_LAUNCH((k_gemm_outer<4, DEV, SET, SC, EPI>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
-  else if (a.m <= 8)
-    SSP_LAUNCH((k_gemm_outer<8, DEV, SET, SC, EPI>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
-  else
-    SSP_LAUNCH((k_gemm_outer<16, DEV, SET, SC, EPI>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
-}
-
-template <bool SC>
-void launch_outer_sc(ssp_ctx* ctx, unsigned grid, const OuterArgs& a) {
-  if (a.alpha_dev)
-    a.set ? launch_outer_t<true, true, SC>(ctx, grid, a) : launch_outer_t<true, false, SC>(ctx, grid, a);
-  else
-    a.set ? launch_outer_t<false, true, SC>(ctx, grid, a) : launch_outer_t<false, false, SC>(ctx, grid, a);
-}
-
-// The norm-carrying instances (NRM): the unscaled write-only form up to 8 destinations, with or without
-// the epilogue.  16 destinations run 2-position windows and would need 128 KiB of LDS: not built.
-constexpr int kOuterNormDst = 8;
-unsigned outer_norm_grid(const ssp_ctx* ctx, size_t n) { return ssp::win_grid(ctx, n, ssp::kDotU, 8); }
-
-template <bool DEV, bool EPI>
-void launch_outer_nrm(ssp_ctx* ctx, unsigned grid, const OuterArgs& a) {
-  if (a.m <= 1)
-    SSP_LAUNCH((k_gemm_outer<1, DEV, true, false, EPI, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
-  else if (a.m <= 2)
-    SSP_LAUNCH((k_gemm_outer<2, DEV, true, false, EPI, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
-  else if (a.m <= 4)
-    SSP_LAUNCH((k_gemm_outer<4, DEV, true, false, EPI, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
-  else
-    SSP_LAUNCH((k_gemm_outer<8, DEV, true, false, EPI, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
-}
-
-int launch_outer(ssp_ctx* ctx, const OuterArgs& a) {
-  if (a.partial) {  // a flushed record launched by the dot of one of its destinations: k_dot_partial's grid
-    if (!a.set || a.scale_dev || a.m > kOuterNormDst || (a.epi_mask && a.k + a.m > ssp::kOuterSrc))
-      return ssp::set_error(SSP_ERR_ARG, "gemm_outer: norms on a launch that cannot carry them");
-    const unsigned grid = outer_norm_grid(ctx, a.n);
-    if (a.epi_mask)
-      a.alpha_dev ? launch_outer_nrm<true, true>(ctx, grid, a) : launch_outer_nrm<false, true>(ctx, grid, a);
-    else
-      a.alpha_dev ? launch_outer_nrm<true, false>(ctx, grid, a) : launch_outer_nrm<false, false>(ctx, grid, a);
-    SSP_TRY_HIP(hipGetLastError());
-    return SSP_OK;
-  }
-  // workgroups per CU of the launch: ctx->outer_per_cu (SSP_OUTER_WG_PER_CU at context creation)
-  const unsigned grid = ssp::stream_grid(ctx, a.n / 2 + 1, kOuterWin, unsigned(ctx->outer_per_cu));
-  if (a.epi_mask) {  // a flushed record with ssp_axpy terms: write-only, unscaled, its epilogue sources in place
-    if (!a.set || a.scale_dev || a.k + a.m > ssp::kOuterSrc)
-      return ssp::set_error(SSP_ERR_ARG, "gemm_outer: epilogue terms on a launch that cannot carry them");
-    a.alpha_dev ? launch_outer_t<true, true, false, true>(ctx, grid, a)
-                : launch_outer_t<false, true, false, true>(ctx, grid, a);
-    SSP_TRY_HIP(hipGetLastError());
-    return SSP_OK;
-  }
-  a.scale_dev ? launch_outer_sc<true>(ctx, grid, a) : launch_outer_sc<false>(ctx, grid, a);
-  SSP_TRY_HIP(hipGetLastError());
-  return SSP_OK;
-}
-
 // SSP_LEDGER_DETAIL tags: the kernel instance and the panel's shape
 int ng_inst(int need) { return need <= 4 ? need : need <= 6 ? 6 : need <= 8 ? 8 : need <= 12 ? 12 : 16; }
-std::string shape_tag(const char* kind, int a, int b, int c, int d, bool sc) {
-  char t[96];
-  std::snprintf(t, sizeof(t), "%s<%d,%d> %dx%d%s", kind, a, b, c, d, sc ? " sc" : "");
-  return t;
-}
-
-bool any_scaled(const double* s, int n) {
-  for (int i = 0; s && i < n; ++i)
-    if (s[i] != 1.0) return true;
-  return false;
-}
 
 }  // namespace
 
@@ -1508,8 +1141,8 @@ int ssp_gemm_inner_scaled(ssp_ctx* ctx, const double* const* xx, const double* x
   if (m < 0 || k < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_gemm_inner: negative dimension");
   if (m * k > 0 && !out) return ssp::set_error(SSP_ERR_ARG, "ssp_gemm_inner: null out");
   if (m == 0 || k == 0) return SSP_OK;
-  SSP_TRY(check_ptrs(xx, m, n, "ssp_gemm_inner"));
-  SSP_TRY(check_ptrs(yy, k, n, "ssp_gemm_inner"));
+  SSP_TRY(ssp::check_ptrs(xx, m, n, "ssp_gemm_inner"));
+  SSP_TRY(ssp::check_ptrs(yy, k, n, "ssp_gemm_inner"));
   // Put the shorter side on the MFMA rows (groups of 4, at most 16 per launch), the longer on the columns.
   const bool swap = m > k;
   const double* const* rows = swap ? yy : xx;
@@ -1519,7 +1152,7 @@ int ssp_gemm_inner_scaled(ssp_ctx* ctx, const double* const* xx, const double* x
   std::vector<double> rs(size_t(R), 1.0), cs(size_t(C), 1.0);
   for (int i = 0; i < m; ++i) (swap ? cs : rs)[size_t(i)] = xs ? xs[i] : 1.0;
   for (int j = 0; j < k; ++j) (swap ? rs : cs)[size_t(j)] = ys ? ys[j] : 1.0;
-  const bool sc = any_scaled(rs.data(), R) || any_scaled(cs.data(), C);
+  const bool sc = ssp::any_scaled(rs.data(), R) || ssp::any_scaled(cs.data(), C);
   // Column prefix (k_gemm_inner PRE): when the first R columns are the rows themselves (the batched
   // overlap rows [params, actions, Q, ...] against params), the panel takes them from the row
   // registers.  The columns are laid out with 4 ceil(R / 4) - R padding columns after that prefix
@@ -1614,7 +1247,7 @@ int ssp_gemm_inner_scaled(ssp_ctx* ctx, const double* const* xx, const double* x
         const unsigned grid = inner_grid(ctx, n);
         SSP_TRY(ssp::ensure_partial(ctx, size_t(grid) * m * m));
         a.partial = ctx->partial;
-        ls.detail(shape_tag("sym", (m + 3) / 4, (m + 3) / 4, m, m, sc));
+        ls.detail(ssp::shape_tag("sym", (m + 3) / 4, (m + 3) / 4, m, m, sc));
         SSP_TRY(launch_inner_sym(ctx, a, grid, sc));
         SSP_TRY(ssp::launch_reduce_partials(ctx, ctx->partial, int(grid), m, m, ctx->result_dev, m, 0, 0, &tail, true));
       }
@@ -1634,13 +1267,13 @@ int ssp_gemm_inner_scaled(ssp_ctx* ctx, const double* const* xx, const double* x
             a.y[j] = cols[c0 + j];
             a.ys[j] = cs[size_t(c0 + j)];
           }
-          const bool sc_launch = any_scaled(a.xs, a.m) || any_scaled(a.ys, a.k);
+          const bool sc_launch = ssp::any_scaled(a.xs, a.m) || ssp::any_scaled(a.ys, a.k);
           const unsigned grid = inner_grid(ctx, n);
           SSP_TRY(ssp::ensure_partial(ctx, size_t(grid) * a.m * a.k));
           a.partial = ctx->partial;
           const bool pre = pad >= 0 && c0 == 0;
           if (r0 == 0 && c0 == 0)
-            ls.detail(shape_tag(pre ? "mfma-pre" : "mfma", (a.m + 3) / 4, ng_inst((a.k + 3) / 4), a.m, a.k, sc_launch));
+            ls.detail(ssp::shape_tag(pre ? "mfma-pre" : "mfma", (a.m + 3) / 4, ng_inst((a.k + 3) / 4), a.m, a.k, sc_launch));
           SSP_TRY(launch_inner(ctx, a, grid, sc_launch, pre));
           const bool last = r0 + ssp::kInnerRows >= R && c0 + cols_per_launch >= C2;
           SSP_TRY(ssp::launch_reduce_partials(ctx, ctx->partial, int(grid), a.m, a.k, ctx->result_dev, C2, r0, c0, &tail,
@@ -1670,237 +1303,12 @@ int ssp_gemm_inner_scaled(ssp_ctx* ctx, const double* const* xx, const double* x
   return SSP_OK;
 }
 
-}  // extern "C"
-
-namespace {
-// The launch of a flushed record (pending_outer.h): the write-only kernel its call would have launched,
-// or with attached terms its EPI instantiation, under the call's own ledger row; each term adds one
-// source stream to the row's bytes.
-// norms: as the NRM instance, whose fold delivers the m sums of squares as `tail` says.
-int launch_record(ssp_ctx* ctx, const ssp::PendingOuter::Record& r, const ssp::FoldTail* norms = nullptr) {
-  const int e = r.terms();
-  ssp::LedgerScope ls(ctx, r.set ? "gemm_outer_set" : "gemm_outer", 8.0 * r.n * (r.k + r.m + e));
-  OuterArgs a{};
-  a.k = r.k;
-  a.m = r.m;
-  a.set = 1;
-  a.n = r.n;
-  for (int i = 0; i < r.k; ++i) a.x[i] = r.x[i];
-  for (int j = 0; j < r.m; ++j) a.y[j] = r.y[j];
-  if (e > 0) {  // attach() has checked that the epilogue sources fit behind the k sources
-    a.epi_mask = int(r.mask);
-    for (int j = 0; j < r.m; ++j) {
-      const bool on = (r.mask >> j) & 1u;
-      a.x[r.k + j] = on ? r.ex[j] : nullptr;
-      a.epi[j] = on ? r.ea[j] : 0.0;
-    }
-  }
-  const bool dev = r.k * r.m > ssp::kOuterAlpha;
-  if (dev) {
-    void* p;
-    SSP_TRY(ssp::upload_small(ctx, r.alpha, size_t(r.k) * r.m * sizeof(double), &p));
-    a.alpha_dev = static_cast<const double*>(p);
-    SSP_TRY(ssp::flush_uploads(ctx));
-  } else {
-    std::copy(r.alpha, r.alpha + r.k * r.m, a.alpha);
-  }
-  const int mi = a.m <= 1 ? 1 : a.m <= 2 ? 2 : a.m <= 4 ? 4 : a.m <= 8 ? 8 : 16;
-  std::string tag = shape_tag(dev ? "dev" : "arg", mi, a.set, a.k, a.m, false);
-  if (e > 0) tag += " epi" + std::to_string(e);
-  if (norms) {
-    a.partial = ctx->partial;
-    a.tail = *norms;
-    tag += " nrm";
-  }
-  ls.detail(tag);
-  return launch_outer(ctx, a);
-}
-}  // namespace
-
-namespace ssp {
-int flush_outer(ssp_ctx* ctx) {
-  ctx->outer_norms.forget();
-  if (!ctx->pending_outer.pending()) return SSP_OK;
-  int status = SSP_OK;
-  ctx->pending_outer.flush([&](const PendingOuter::Record& r) { status = launch_record(ctx, r); });
-  return status;
-}
-
-bool outer_norms_apply(const ssp_ctx* ctx, const double* y, size_t n) {
-  if (!ctx->outer_norms_on || !ctx->pending_outer.pending()) return false;
-  const PendingOuter::Record& r = ctx->pending_outer.record();
-  if (r.m > kOuterNormDst || n != r.n) return false;
-  for (int j = 0; j < r.m; ++j)
-    if (r.y[j] == y) return true;
-  return false;
-}
-
-int launch_outer_norms(ssp_ctx* ctx) {
-  ctx->outer_norms.forget();
-  if (!ctx->pending_outer.pending()) return SSP_OK;
-  const PendingOuter::Record& r = ctx->pending_outer.record();
-  const int m = r.m;
-  const bool ranks = comm_attached(ctx);
-  FoldTail tail{};
-  int status = ensure_partial(ctx, size_t(outer_norm_grid(ctx, r.n)) * m);
-  if (status == SSP_OK) status = fold_begin(ctx, m, &tail);
-  if (status == SSP_OK && ranks) {
-    // rank-local sums: each served dot reduces its own over the ranks, as the dot it replaces does
-    if (!ctx->norms_dev && hipMalloc(reinterpret_cast<void**>(&ctx->norms_dev), kOuterDst * sizeof(double)) != hipSuccess)
-      status = set_error(SSP_ERR_NOMEM, "hipMalloc of the norm staging failed");
-    tail.out = ctx->norms_dev;
-  }
-  if (status != SSP_OK) {  // the record is launched as it always was, and the dot runs by itself
-    const int plain = flush_outer(ctx);
-    return plain != SSP_OK ? plain : status;
-  }
-  ctx->outer_norms.keep(r.y, m, r.n);
-  ctx->pending_outer.flush([&](const PendingOuter::Record& rec) { status = launch_record(ctx, rec, &tail); });
-  if (status == SSP_OK && !ranks) {
-    // one wait for all m sums, before anything else can reuse the host result buffer
-    double v[kOuterDst];
-    status = fold_finish(ctx, tail, v);
-    if (status == SSP_OK) ctx->outer_norms.set_values(v);
-  }
-  if (status != SSP_OK) ctx->outer_norms.forget();
-  return status;
-}
-}  // namespace ssp
-
-namespace {
-int gemm_outer_impl(ssp_ctx* ctx, const double* alphas, const double* const* xx, const double* xs, int k,
-                    double* const* yy, const double* ys, int m, size_t n, bool set) {
-  SSP_CHECK_CTX_KEEP_FILLS(ctx);
-  if (m < 0 || k < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_gemm_outer: negative dimension");
-  if (set && k == 0) {
-    // These zero fills may stay deferred past the return, like a caller's own ssp_fill(0): the next
-    // library call stores them.  A caller that hands yy on to code of its own (the host layer's
-    // data_wo() destinations reaching a user's action) relies on the rule of include/subspace_hip.h:
-    // take ssp_ctx_stream or ssp_synchronize before foreign code touches the memory.
-    for (int j = 0; j < m; ++j) SSP_TRY(ssp_fill(ctx, 0.0, yy[j], n));
-    return SSP_OK;
-  }
-  if (m == 0 || n == 0) return SSP_OK;
-  if (k == 0) {  // no sources: the destinations' deferred scales still have to be stored
-    for (int j = 0; j < m; ++j)
-      if (!set && ys && ys[j] != 1.0) SSP_TRY(ssp_scal(ctx, ys[j], yy[j], n));
-    return SSP_OK;
-  }
-  if (!alphas) return ssp::set_error(SSP_ERR_ARG, "ssp_gemm_outer: null alphas");
-  SSP_TRY(check_ptrs(xx, k, n, "ssp_gemm_outer"));
-  SSP_TRY(check_ptrs(const_cast<const double* const*>(yy), m, n, "ssp_gemm_outer"));
-  for (int j = 0; j < m; ++j)
-    for (int i = 0; i < k; ++i)
-      if (yy[j] == xx[i]) return ssp::set_error(SSP_ERR_ARG, "ssp_gemm_outer: a destination aliases a source");
-  // Pending zero fills (pending_fill.h).  The sources are read: theirs are stored.  The write-only
-  // form overwrites its destinations: the entries inside them are dropped.  The read-modify-write form
-  // consumes: when every destination is exactly a pending entry (so they are distinct and disjoint),
-  // carries no deferred scale and is outside exact mode, the entries are dropped and the first source
-  // chunk of every destination group runs as the SET instantiation, whose accumulators start from the
-  // +0.0 that the read-modify-write form would have loaded -- the same bits without writing the zeros
-  // and reading them back.  All or nothing: otherwise every entry a destination touches is stored and
-  // the call runs as it always did.  Entries no operand touches stay pending.
-  bool consume = false;
-  if (!ctx->pending_fills.empty()) {
-    for (int i = 0; i < k; ++i) SSP_TRY(ssp::flush_fills_over(ctx, xx[i], n));
-    if (set) {
-      for (int j = 0; j < m; ++j) SSP_TRY(ssp::overwrite_fills(ctx, yy[j], n));
-    } else {
-      consume = !any_scaled(ys, m) && !ssp::exact_mode(ctx, n);
-      for (int j = 0; consume && j < m; ++j) {
-        consume = ctx->pending_fills.find_exact(yy[j], n) >= 0;
-        for (int i = 0; consume && i < j; ++i) consume = yy[i] != yy[j];
-      }
-      for (int j = 0; j < m; ++j) {
-        if (consume) ctx->pending_fills.erase(ctx->pending_fills.find_exact(yy[j], n));
-        else SSP_TRY(ssp::flush_fills_over(ctx, yy[j], n));
-      }
-    }
-  }
-  const bool set0 = set || consume;  // the destinations are not read by their first launch
-  // Deferred gemm_outer (pending_outer.h): the unscaled write-only form of one launch is recorded, not
-  // launched, so that the ssp_axpy calls that follow on its destinations ride on its stores; whatever
-  // else comes next launches it first (ssp::flush_outer, under this call's ledger row).  Everything
-  // above has happened as for the launch, so no pending zero fill overlaps an operand of the record.
-  if (ctx->defer_outer && set0 && !any_scaled(xs, k) && !ssp::exact_mode(ctx, n) &&
-      ctx->pending_outer.record(alphas, xx, k, yy, m, n, set))
-    return SSP_OK;
-  // Destinations are independent; sources are applied in increasing order, in groups that fit
-  // the kernel argument block, so each destination sees the reference's summation order.
-  ssp::LedgerScope ls(ctx, set ? "gemm_outer_set" : "gemm_outer", 8.0 * n * (k + (set0 ? 1.0 : 2.0) * m));
-  if (ssp::exact_mode(ctx, n)) return ssp::exact_outer(ctx, alphas, xx, xs, k, yy, ys, m, n, set);
-  for (int j0 = 0; j0 < m; j0 += ssp::kOuterDst) {
-    const int mm = std::min(ssp::kOuterDst, m - j0);
-    // Up to kOuterSrc sources per launch; their alphas ride in the argument block when they fit,
-    // else in device memory (one upload), so every destination is read and written once per
-    // kOuterSrc sources.
-    for (int i0 = 0; i0 < k; i0 += ssp::kOuterSrc) {
-      OuterArgs a{};
-      a.m = mm;
-      a.k = std::min(ssp::kOuterSrc, k - i0);
-      a.set = (set0 && i0 == 0) ? 1 : 0;
-      a.n = n;
-      for (int i = 0; i < a.k; ++i) a.x[i] = xx[i0 + i];
-      for (int j = 0; j < mm; ++j) a.y[j] = yy[j0 + j];
-      // deferred scales: every source's; the destinations' on their first read only (i0 == 0)
-      std::vector<double> scl(size_t(a.k + mm), 1.0);
-      for (int i = 0; i < a.k; ++i) scl[size_t(i)] = xs ? xs[i0 + i] : 1.0;
-      for (int j = 0; j < mm; ++j) scl[size_t(a.k + j)] = (ys && i0 == 0 && !set0) ? ys[j0 + j] : 1.0;
-      if (any_scaled(scl.data(), int(scl.size()))) {
-        void* ps;
-        SSP_TRY(ssp::upload_small(ctx, scl.data(), scl.size() * sizeof(double), &ps));
-        a.scale_dev = static_cast<const double*>(ps);
-      }
-      const bool dev = a.k * mm > ssp::kOuterAlpha;
-      std::vector<double> block(dev ? size_t(a.k) * mm : 0);
-      double* dst = dev ? block.data() : a.alpha;
-      for (int i = 0; i < a.k; ++i)
-        for (int j = 0; j < mm; ++j) dst[i * mm + j] = alphas[size_t(i0 + i) * m + j0 + j];
-      if (dev) {
-        void* p;
-        SSP_TRY(ssp::upload_small(ctx, block.data(), block.size() * sizeof(double), &p));
-        a.alpha_dev = static_cast<const double*>(p);
-      }
-      SSP_TRY(ssp::flush_uploads(ctx));
-      if (j0 == 0 && i0 == 0) {
-        const int mi = a.m <= 1 ? 1 : a.m <= 2 ? 2 : a.m <= 4 ? 4 : a.m <= 8 ? 8 : 16;
-        ls.detail(shape_tag(dev ? "dev" : "arg", mi, a.set, a.k, mm, a.scale_dev != nullptr));
-      }
-      SSP_TRY(launch_outer(ctx, a));
-    }
-  }
-  return SSP_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int ssp_gemm_outer(ssp_ctx* ctx, const double* alphas, const double* const* xx, int k, double* const* yy, int m,
-                   size_t n) {
-  return gemm_outer_impl(ctx, alphas, xx, nullptr, k, yy, nullptr, m, n, false);
-}
-
-int ssp_gemm_outer_set(ssp_ctx* ctx, const double* alphas, const double* const* xx, int k, double* const* yy, int m,
-                       size_t n) {
-  return gemm_outer_impl(ctx, alphas, xx, nullptr, k, yy, nullptr, m, n, true);
-}
-
-int ssp_gemm_outer_scaled(ssp_ctx* ctx, const double* alphas, const double* const* xx, const double* xs, int k,
-                          double* const* yy, const double* ys, int m, size_t n) {
-  return gemm_outer_impl(ctx, alphas, xx, xs, k, yy, ys, m, n, false);
-}
-
-int ssp_gemm_outer_set_scaled(ssp_ctx* ctx, const double* alphas, const double* const* xx, const double* xs, int k,
-                              double* const* yy, int m, size_t n) {
-  return gemm_outer_impl(ctx, alphas, xx, xs, k, yy, nullptr, m, n, true);
-}
-
 int ssp_scal_inner(ssp_ctx* ctx, double alpha, double* x, const double* const* yy, int m, size_t n, double* out) {
   SSP_CHECK_CTX(ctx);
   if (m < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_scal_inner: negative dimension");
   if (m > 0 && !out) return ssp::set_error(SSP_ERR_ARG, "ssp_scal_inner: null out");
-  SSP_TRY(check_ptrs(const_cast<const double* const*>(&x), 1, n, "ssp_scal_inner"));
-  SSP_TRY(check_ptrs(yy, m, n, "ssp_scal_inner"));
+  SSP_TRY(ssp::check_ptrs(const_cast<const double* const*>(&x), 1, n, "ssp_scal_inner"));
+  SSP_TRY(ssp::check_ptrs(yy, m, n, "ssp_scal_inner"));
   for (int j = 0; j < m; ++j)
     if (yy[j] == x) return ssp::set_error(SSP_ERR_ARG, "ssp_scal_inner: a vector of yy aliases x");
   // no dots, more than one launch, or the reference's arithmetic (short vectors): the unfused pair
@@ -1943,8 +1351,8 @@ int ssp_axpy_norm(ssp_ctx* ctx, const double* c, const double* x, double* const*
   SSP_CHECK_CTX(ctx);
   if (m < 1) return ssp::set_error(SSP_ERR_ARG, "ssp_axpy_norm: needs at least one destination");
   if (!c || !out) return ssp::set_error(SSP_ERR_ARG, "ssp_axpy_norm: null coefficients or out");
-  SSP_TRY(check_ptrs(&x, 1, n, "ssp_axpy_norm"));
-  SSP_TRY(check_ptrs(const_cast<const double* const*>(yy), m, n, "ssp_axpy_norm"));
+  SSP_TRY(ssp::check_ptrs(&x, 1, n, "ssp_axpy_norm"));
+  SSP_TRY(ssp::check_ptrs(const_cast<const double* const*>(yy), m, n, "ssp_axpy_norm"));
   for (int j = 0; j < m; ++j)
     if (yy[j] == x) return ssp::set_error(SSP_ERR_ARG, "ssp_axpy_norm: a destination aliases x");
   if (m > ssp::kOuterDst || ssp::exact_mode(ctx, n)) {  // more than one launch / short vectors: the unfused pair
@@ -1990,8 +1398,8 @@ int ssp_axpy_gram(ssp_ctx* ctx, const double* c, double* x, double xs, int store
   SSP_CHECK_CTX(ctx);
   if (m < 1) return ssp::set_error(SSP_ERR_ARG, "ssp_axpy_gram: needs at least one destination");
   if (!c || !out) return ssp::set_error(SSP_ERR_ARG, "ssp_axpy_gram: null coefficients or out");
-  SSP_TRY(check_ptrs(const_cast<const double* const*>(&x), 1, n, "ssp_axpy_gram"));
-  SSP_TRY(check_ptrs(const_cast<const double* const*>(yy), m, n, "ssp_axpy_gram"));
+  SSP_TRY(ssp::check_ptrs(const_cast<const double* const*>(&x), 1, n, "ssp_axpy_gram"));
+  SSP_TRY(ssp::check_ptrs(const_cast<const double* const*>(yy), m, n, "ssp_axpy_gram"));
   for (int j = 0; j < m; ++j) {
     if (yy[j] == x) return ssp::set_error(SSP_ERR_ARG, "ssp_axpy_gram: a destination aliases x");
     for (int i = 0; i < j; ++i)
@@ -2046,8 +1454,8 @@ int ssp_axpy_pairs_norm(ssp_ctx* ctx, const double* c, const double* const* xx, 
   if (m < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_axpy_pairs_norm: negative dimension");
   if (m == 0) return SSP_OK;
   if (!c || !out) return ssp::set_error(SSP_ERR_ARG, "ssp_axpy_pairs_norm: null coefficients or out");
-  SSP_TRY(check_ptrs(xx, m, n, "ssp_axpy_pairs_norm"));
-  SSP_TRY(check_ptrs(const_cast<const double* const*>(yy), m, n, "ssp_axpy_pairs_norm"));
+  SSP_TRY(ssp::check_ptrs(xx, m, n, "ssp_axpy_pairs_norm"));
+  SSP_TRY(ssp::check_ptrs(const_cast<const double* const*>(yy), m, n, "ssp_axpy_pairs_norm"));
   for (int j = 0; j < m; ++j)
     for (int i = 0; i < m; ++i)
       if (yy[j] == xx[i] || (i < j && yy[i] == yy[j]))
@@ -2111,9 +1519,9 @@ int ssp_axpy_inner(ssp_ctx* ctx, const double* c, const double* x, double* const
   if (m < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_axpy_inner: negative dimension");
   if (m == 0) return SSP_OK;
   if (!c || !out) return ssp::set_error(SSP_ERR_ARG, "ssp_axpy_inner: null coefficients or out");
-  SSP_TRY(check_ptrs(&x, 1, n, "ssp_axpy_inner"));
-  SSP_TRY(check_ptrs(&z, 1, n, "ssp_axpy_inner"));
-  SSP_TRY(check_ptrs(const_cast<const double* const*>(yy), m, n, "ssp_axpy_inner"));
+  SSP_TRY(ssp::check_ptrs(&x, 1, n, "ssp_axpy_inner"));
+  SSP_TRY(ssp::check_ptrs(&z, 1, n, "ssp_axpy_inner"));
+  SSP_TRY(ssp::check_ptrs(const_cast<const double* const*>(yy), m, n, "ssp_axpy_inner"));
   for (int j = 0; j < m; ++j)
     if (yy[j] == x || yy[j] == z) return ssp::set_error(SSP_ERR_ARG, "ssp_axpy_inner: a destination aliases x or z");
   if (ssp::exact_mode(ctx, n)) {  // short vectors: the reference's arithmetic, one reduction
@@ -2174,7 +1582,7 @@ int transform_impl(ssp_ctx* ctx, const double* t, double* const* xx, const doubl
   SSP_CHECK_CTX(ctx);
   if (m < 1 || m > 8) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": 1 <= m <= 8");
   if (!t) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null t");
-  SSP_TRY(check_ptrs(const_cast<const double* const*>(xx), m, n, what));
+  SSP_TRY(ssp::check_ptrs(const_cast<const double* const*>(xx), m, n, what));
   for (int j = 0; j < m; ++j)
     for (int i = 0; i < j; ++i)
       if (xx[i] == xx[j]) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": repeated vector");
@@ -2204,7 +1612,7 @@ int transform_impl(ssp_ctx* ctx, const double* t, double* const* xx, const doubl
       a.partial = ctx->partial;
       if (!pass) a.tail = tail;  // else the kernel leaves its partials to the reduce pass below
     }
-    ls.detail(shape_tag("transform", m, fused, m, m, xs != nullptr));
+    ls.detail(ssp::shape_tag("transform", m, fused, m, m, xs != nullptr));
     launch_transform(ctx, m, grid, a, fused, exact, pass);
     SSP_TRY_HIP(hipGetLastError());
     if (pass)  // one workgroup per pair dot, publishing to the host (as the gemm_inner panels)
@@ -2271,8 +1679,8 @@ int ssp_precondition_norms(ssp_ctx* ctx, double* const* a, int nvec, const doubl
     }
     return ssp::fold_finish(ctx, tail, norms2);
   }
-  SSP_TRY(check_ptrs(&d, 1, n, "ssp_precondition_norms"));
-  SSP_TRY(check_ptrs(const_cast<const double* const*>(a), nvec, n, "ssp_precondition_norms"));
+  SSP_TRY(ssp::check_ptrs(&d, 1, n, "ssp_precondition_norms"));
+  SSP_TRY(ssp::check_ptrs(const_cast<const double* const*>(a), nvec, n, "ssp_precondition_norms"));
   PrecNormArgs p{};
   p.nvec = nvec;
   for (int v = 0; v < nvec; ++v) {

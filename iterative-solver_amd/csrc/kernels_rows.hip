@@ -33,21 +33,9 @@ struct RowsArgs {
   size_t n;
 };
 
-__device__ __forceinline__ double2 ld2(const double* p) { return *reinterpret_cast<const double2*>(p); }
-__device__ __forceinline__ void st2(double* p, double2 v) { *reinterpret_cast<double2*>(p) = v; }
+using ssp::ld2, ssp::sc1, ssp::sc2, ssp::st2;  // QT: the value k_quantise_f32 stores
 __device__ __forceinline__ double ld1nt(const double* p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ void st1nt(double* p, double v) { __builtin_nontemporal_store(v, p); }
-// QT: the product (or the element) rounded through binary32, the value k_quantise_f32 stores.
-template <bool SC, bool QT = false>
-__device__ __forceinline__ double sc1(double v, double s) {
-  const double p = SC ? v * s : v;
-  return QT ? double(float(p)) : p;
-}
-template <bool SC, bool QT = false>
-__device__ __forceinline__ double2 sc2(double2 v, double s) {
-  return make_double2(sc1<SC, QT>(v.x, s), sc1<SC, QT>(v.y, s));
-}
-
 // Both sides 16-byte aligned: k_copy's loop (WIN: k_copy_win's).
 template <bool SC, bool WIN, bool QT = false>
 __device__ __forceinline__ void row_copy16(double* __restrict__ x, const double* __restrict__ y, size_t n, double s) {

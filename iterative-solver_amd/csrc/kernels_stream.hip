@@ -20,24 +20,11 @@
 namespace {
 
 using ssp::kBlock;
-
-__device__ __forceinline__ double2 ld2(const double* p) { return *reinterpret_cast<const double2*>(p); }
-__device__ __forceinline__ void st2(double* p, double2 v) { *reinterpret_cast<double2*>(p) = v; }
-// Deferred scal (include/subspace_hip.h): v * s is the one rounding an eager scal would have stored.
-template <bool SC>
-__device__ __forceinline__ double2 sc2(double2 v, double s) {
-  return SC ? make_double2(v.x * s, v.y * s) : v;
-}
-template <bool SC>
-__device__ __forceinline__ double sc1(double v, double s) {
-  return SC ? v * s : v;
-}
-
+using ssp::ld2, ssp::sc1, ssp::sc2, ssp::st2;
 // Window shape: a wave covers kWinU x 64 consecutive double2 (kWinU KiB) of each vector per visit.
 using ssp::kWinMin;
 using ssp::kWinU;
 using ssp::kDotU;
-
 
 // Sum over the 256 threads of a workgroup; result valid in thread 0.  Fixed order.
 __device__ __forceinline__ double block_sum(double v) {
@@ -328,13 +315,6 @@ __global__ __launch_bounds__(kBlock) void k_precondition(const PrecArgs p) {
       });
 }
 
-int check_vec(const void* p, size_t n, const char* what) {
-  if (n == 0) return SSP_OK;
-  if (!p) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null vector");
-  if (!ssp::aligned16(p)) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": vector not 16-byte aligned");
-  return SSP_OK;
-}
-
 }  // namespace
 
 namespace ssp {
@@ -353,7 +333,7 @@ int launch_reduce_partials(ssp_ctx* ctx, const double* partial, int nblocks, int
   return SSP_OK;
 }
 int fill_now(ssp_ctx* ctx, double alpha, double* x, size_t n) {
-  SSP_TRY(check_vec(x, n, "ssp_fill"));
+  SSP_TRY(ssp::check_vec(x, n, "ssp_fill"));
   if (n == 0) return SSP_OK;
   LedgerScope ls(ctx, "fill", 8.0 * n);
   SSP_LAUNCH(k_fill, dim3(stream_grid(ctx, n / 2 + 1, 1, 64)), dim3(kBlock), 0, ctx->stream, x, n, alpha);
@@ -404,7 +384,7 @@ int ssp_fill(ssp_ctx* ctx, double alpha, double* x, size_t n) {
   // next entry point stores it, unless it is one that overwrites or consumes it.  -0.0 and short
   // vectors keep the eager launch (fill_now validates x for that path).
   if (ctx->defer_fill && n > 0 && alpha == 0.0 && !std::signbit(alpha) && !ssp::exact_mode(ctx, n)) {
-    SSP_TRY(check_vec(x, n, "ssp_fill"));
+    SSP_TRY(ssp::check_vec(x, n, "ssp_fill"));
     ssp::FillFlusher f{ctx};
     ctx->pending_fills.insert(x, n, f);
     return f.status;
@@ -415,7 +395,7 @@ int ssp_fill(ssp_ctx* ctx, double alpha, double* x, size_t n) {
 
 int ssp_scal(ssp_ctx* ctx, double alpha, double* x, size_t n) {
   SSP_CHECK_CTX(ctx);
-  SSP_TRY(check_vec(x, n, "ssp_scal"));
+  SSP_TRY(ssp::check_vec(x, n, "ssp_scal"));
   if (n == 0) return SSP_OK;
   ssp::LedgerScope ls(ctx, "scal", 16.0 * n);
   if (n >= kWinMin)
@@ -431,8 +411,8 @@ int ssp_scal(ssp_ctx* ctx, double alpha, double* x, size_t n) {
 namespace {
 int copy_impl(ssp_ctx* ctx, double alpha, double* x, const double* y, size_t n, bool scaled, const char* what) {
   SSP_CHECK_CTX_KEEP_FILLS(ctx);
-  SSP_TRY(check_vec(x, n, what));
-  SSP_TRY(check_vec(y, n, what));
+  SSP_TRY(ssp::check_vec(x, n, what));
+  SSP_TRY(ssp::check_vec(y, n, what));
   if (n == 0 || (x == y && !scaled)) return SSP_OK;
   if (x == y) return ssp_scal(ctx, alpha, x, n);
   // pending zero fills: the source is read, so its are stored; x is overwritten whole and never read,
@@ -456,20 +436,15 @@ int copy_impl(ssp_ctx* ctx, double alpha, double* x, const double* y, size_t n, 
 int axpy_impl(ssp_ctx* ctx, double alpha, const double* x, double xs, double* y, double ys, size_t n,
               const char* what) {
   SSP_CHECK_CTX_KEEP_ALL(ctx);
-  ctx->outer_norms.forget();  // this prologue launches no record: y may be a vector whose norm is kept
+  // Deferred gemm_outer (pending_outer.h): the axpy that becomes an epilogue term of the pending record launches
+  // nothing.  Any other axpy finds the record launched, and stores every fill, as the default prologue does.
+  bool attached = false;
+  SSP_TRY(ssp::outer_take_axpy(ctx, alpha, x, xs, y, ys, n, &attached));
+  if (attached) return SSP_OK;
   const bool sc = xs != 1.0 || ys != 1.0;
-  // Deferred gemm_outer (pending_outer.h): an unscaled axpy onto exactly one destination of the pending
-  // record becomes its epilogue term and launches nothing; x is read by that launch, so its pending
-  // zero fills are stored first.  Any other axpy launches the record, and stores every fill, as the
-  // default prologue does.
-  if (ctx->pending_outer.pending()) {
-    const bool valid = n > 0 && x && y && ssp::aligned16(x) && ssp::aligned16(y);
-    if (valid && !sc && ctx->pending_outer.attach(alpha, x, y, n)) return ssp::flush_fills_over(ctx, x, n);
-    SSP_TRY(ssp::flush_outer(ctx));
-  }
   SSP_TRY(ssp::flush_fills(ctx));
-  SSP_TRY(check_vec(x, n, what));
-  SSP_TRY(check_vec(y, n, what));
+  SSP_TRY(ssp::check_vec(x, n, what));
+  SSP_TRY(ssp::check_vec(y, n, what));
   if (n == 0) return SSP_OK;
   ssp::LedgerScope ls(ctx, "axpy", 24.0 * n);
   if (ssp::exact_mode(ctx, n)) return ssp::exact_outer(ctx, &alpha, &x, &xs, 1, &y, &ys, 1, n, false);
@@ -489,30 +464,17 @@ int axpy_impl(ssp_ctx* ctx, double alpha, const double* x, double xs, double* y,
 int dot_impl(ssp_ctx* ctx, const double* x, double xs, const double* y, double ys, size_t n, double* out,
              const char* what) {
   SSP_CHECK_CTX_KEEP_ALL(ctx);
-  // Norms from the deferred gemm_outer (outer_norms.h): the unscaled dot of a vector with itself that
-  // finds it as a destination of the pending record launches the record as its norm-carrying instance,
-  // and that dot and the same dot of the record's other destinations are answered from the sums it left
-  // (no launch, no ledger row; the pending zero fills stay pending: none overlaps a destination).
-  // Every other dot takes the default prologue, which forgets the sums.
-  if (out && x == y && xs == 1.0 && ys == 1.0) {
-    if (ssp::outer_norms_apply(ctx, y, n)) SSP_TRY(ssp::launch_outer_norms(ctx));
-    const int j = ctx->outer_norms.find(y, n);
-    if (j >= 0) {
-      if (!ssp::comm_attached(ctx)) {
-        *out = ctx->outer_norms.value(j);
-        return SSP_OK;
-      }
-      SSP_TRY(ssp::comm_check(ctx));
-      SSP_TRY(ssp::ensure_result(ctx, 1));
-      SSP_TRY_HIP(hipMemcpyAsync(ctx->result_dev, ctx->norms_dev + j, sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-      return ssp::reduce_fetch(ctx, out, 1);
-    }
-  }
+  // Norms from the deferred gemm_outer (outer_norms.h): a dot answered from the sums its launch left
+  // (no launch of its own, no ledger row; the pending zero fills stay pending: none overlaps a
+  // destination).  Every other dot takes the default prologue, which forgets the sums.
+  bool served = false;
+  SSP_TRY(ssp::outer_serve_dot(ctx, x, xs, y, ys, n, out, &served));
+  if (served) return SSP_OK;
   SSP_TRY(ssp::flush_outer(ctx));
   SSP_TRY(ssp::flush_fills(ctx));
   if (!out) return ssp::set_error(SSP_ERR_ARG, std::string(what) + ": null out");
-  SSP_TRY(check_vec(x, n, what));
-  SSP_TRY(check_vec(y, n, what));
+  SSP_TRY(ssp::check_vec(x, n, what));
+  SSP_TRY(ssp::check_vec(y, n, what));
   if (n == 0) {
     SSP_TRY(ssp::ensure_result(ctx, 1));
     SSP_TRY_HIP(hipMemsetAsync(ctx->result_dev, 0, sizeof(double), ctx->stream));
@@ -574,13 +536,13 @@ int ssp_precondition(ssp_ctx* ctx, double* const* a, int nvec, const double* d, 
   SSP_CHECK_CTX(ctx);
   if (nvec < 0 || (nvec > 0 && (!a || !shift))) return ssp::set_error(SSP_ERR_ARG, "ssp_precondition: bad vectors");
   if (n == 0 || nvec == 0) return SSP_OK;
-  SSP_TRY(check_vec(d, n, "ssp_precondition"));
+  SSP_TRY(ssp::check_vec(d, n, "ssp_precondition"));
   ssp::LedgerScope ls(ctx, "precondition", 8.0 * n * (1 + 2 * nvec));
   for (int v0 = 0; v0 < nvec; v0 += ssp::kPrecVec) {
     PrecArgs p{};
     p.nvec = std::min(ssp::kPrecVec, nvec - v0);
     for (int v = 0; v < p.nvec; ++v) {
-      SSP_TRY(check_vec(a[v0 + v], n, "ssp_precondition"));
+      SSP_TRY(ssp::check_vec(a[v0 + v], n, "ssp_precondition"));
       p.a[v] = a[v0 + v];
       p.shift[v] = shift[v0 + v];
     }

@@ -29,7 +29,24 @@ struct ssp_ledger_entry_t {
 
 namespace ssp {
 struct P2PComm;  // comm_p2p.hip
-}
+
+// The deferred gemm_outer of a context: kernels_outer.hip holds its protocol, context.hip creates, configures
+// and destroys it, and nothing else names its members.  pending: a write-only gemm_outer of one launch recorded
+// instead of launched, so that the ssp_axpy calls on its destinations ride on its stores (pending_outer.h);
+// defer, SSP_DEFER_OUTER=0: launched at once (the same-build A/B, and the eager side of
+// tests/test_deferred_outer_gpu.py).  norms: the norms of the destinations of the last launched record, when
+// the ssp_dot(y, y) of one of them launched it (outer_norms.h): the NRM instance of k_gemm_outer summed them,
+// and the dots of the other destinations are answered from here; norms_on, SSP_OUTER_NORMS=0: off, every dot
+// runs k_dot_partial (the same-build A/B, and the switch case of tests/test_outer_norms_gpu.py).  norms_dev:
+// the rank-local sums when a rank transport is attached (each served dot reduces its own over the ranks).
+struct DeferredOuter {
+  bool defer = true;
+  PendingOuter pending;
+  bool norms_on = true;
+  OuterNorms norms;
+  double* norms_dev = nullptr;
+};
+}  // namespace ssp
 
 struct ssp_ctx {
   int device = 0;
@@ -58,19 +75,7 @@ struct ssp_ctx {
   // at once (the same-build A/B, and the eager side of tests/test_deferred_fill_gpu.py).
   bool defer_fill = true;
   ssp::PendingFills pending_fills;
-  // A write-only gemm_outer of one launch recorded instead of launched, so that the ssp_axpy calls on
-  // its destinations ride on its stores (pending_outer.h); SSP_DEFER_OUTER=0: launched at once (the
-  // same-build A/B, and the eager side of tests/test_deferred_outer_gpu.py).
-  bool defer_outer = true;
-  ssp::PendingOuter pending_outer;
-  // The norms of the destinations of the last launched record, when the ssp_dot(y, y) of one of them
-  // launched it (outer_norms.h): the NRM instance of k_gemm_outer summed them, and the dots of the other
-  // destinations are answered from here.  SSP_OUTER_NORMS=0: off, every dot runs k_dot_partial (the
-  // same-build A/B, and the switch case of tests/test_outer_norms_gpu.py).  norms_dev: the rank-local
-  // sums when a rank transport is attached (each served dot reduces its own over the ranks).
-  bool outer_norms_on = true;
-  ssp::OuterNorms outer_norms;
-  double* norms_dev = nullptr;
+  ssp::DeferredOuter outer;  // the deferred gemm_outer and the norms its launch left (above)
   hipStream_t stream = nullptr;
 
   // HBM arena: freed blocks are kept by rounded size and recycled (Q vectors are created and
@@ -177,17 +182,20 @@ int fill_now(ssp_ctx* ctx, double alpha, double* x, size_t n);
 int flush_fills(ssp_ctx* ctx);
 int flush_fills_over(ssp_ctx* ctx, const void* p, size_t n);
 int overwrite_fills(ssp_ctx* ctx, const void* p, size_t n);
-// Deferred gemm_outer (kernels_panel.hip): launches the context's pending record, if there is one, under
-// its "gemm_outer" / "gemm_outer_set" ledger row.
-// It also forgets the kept norms (outer_norms.h): every entry point but ssp_dot comes through here or
-// forgets them itself (ssp_axpy).
+// Deferred gemm_outer (kernels_outer.hip): launches the context's pending record, if there is one, under its
+// "gemm_outer" / "gemm_outer_set" ledger row.  It also forgets the kept norms (outer_norms.h): every entry
+// point but ssp_dot comes through here or through outer_take_axpy (ssp_axpy).
 int flush_outer(ssp_ctx* ctx);
-// The ssp_dot(y, y, n) that finds a pending record: true when y is exactly one of its destinations, n its
-// length and the norm-carrying instance exists for its width.  launch_outer_norms then launches the
-// record as that instance and keeps the m sums in ctx->outer_norms (one rank: their values, after one
-// wait; ranks: the rank-local sums in ctx->norms_dev).
-bool outer_norms_apply(const ssp_ctx* ctx, const double* y, size_t n);
-int launch_outer_norms(ssp_ctx* ctx);
+// ssp_axpy's prologue: forgets the kept norms; then, with a record pending, attaches y += alpha x to it as an
+// epilogue term and stores the pending zero fills of x (*attached: the caller launches nothing), or launches it.
+int outer_take_axpy(ssp_ctx* ctx, double alpha, const double* x, double xs, double* y, double ys, size_t n,
+                    bool* attached);
+// ssp_dot's prologue: the unscaled dot of y with itself that finds y as a destination of the pending record
+// launches the record as its norm-carrying instance; that dot and the same dot of the record's other
+// destinations are delivered to *out from the sums it left (*served), over the ranks when a transport is
+// attached.  Every other dot is declined, nothing launched or forgotten: the caller takes the default prologue.
+int outer_serve_dot(ssp_ctx* ctx, const double* x, double xs, const double* y, double ys, size_t n, double* out,
+                    bool* served);
 // use_device, then flush_outer and flush_fills.
 int enter(ssp_ctx* ctx);
 int ensure_partial(ssp_ctx* ctx, size_t n_doubles);
@@ -232,7 +240,31 @@ __device__ __forceinline__ void st2nt(double* p, double2 v) {
   const nt_double2 w = {v.x, v.y};
   __builtin_nontemporal_store(w, reinterpret_cast<nt_double2*>(p));
 }
+__device__ __forceinline__ double2 ld2(const double* p) { return *reinterpret_cast<const double2*>(p); }
+__device__ __forceinline__ void st2(double* p, double2 v) { *reinterpret_cast<double2*>(p) = v; }
+// Deferred scal (include/subspace_hip.h *_scaled): v * s is the one rounding an eager scal stores.
+// QT: the product (or the element) rounded through binary32, the value k_quantise_f32 stores.
+template <bool SC, bool QT = false>
+__device__ __forceinline__ double sc1(double v, double s) {
+  const double p = SC ? v * s : v;
+  return QT ? double(float(p)) : p;
+}
+template <bool SC, bool QT = false>
+__device__ __forceinline__ double2 sc2(double2 v, double s) {
+  return make_double2(sc1<SC, QT>(v.x, s), sc1<SC, QT>(v.y, s));
+}
 bool aligned16(const void* p);
+// Argument checks of the entry points (context.hip): a vector of n > 0 elements is non-null and 16-byte
+// aligned; a list of `count` such vectors, of any element type, is non-null.  `what` opens the message.
+int check_vec(const void* p, size_t n, const char* what);
+int check_ptrs(const void* const* v, int count, size_t n, const char* what);
+template <typename T>
+int check_ptrs(const T* const* v, int count, size_t n, const char* what) {
+  return check_ptrs(reinterpret_cast<const void* const*>(v), count, n, what);
+}
+// SSP_LEDGER_DETAIL tags of the panel kernels: "<kind><a,b> cxd[ sc]"; any_scaled: some scale is not 1.
+std::string shape_tag(const char* kind, int a, int b, int c, int d, bool sc);
+bool any_scaled(const double* s, int n);
 
 // Ledger scope: records a start event now and an end event at destruction (when enabled).
 // Two timings (SSP_LEDGER_TIMING, read at context creation):

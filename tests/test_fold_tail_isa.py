@@ -126,7 +126,8 @@ def fold_tail_violations(ins):
 def test_fold_tail_handoff_is_write_through_in_the_isa():
     found, names = 0, []
     with tempfile.TemporaryDirectory() as d:
-        for src in ("kernels_stream.hip", "kernels_panel.hip", "kernels_exact.hip", "kernels_sparse.hip"):
+        for src in ("kernels_stream.hip", "kernels_panel.hip", "kernels_outer.hip", "kernels_exact.hip",
+                    "kernels_sparse.hip"):
             out = os.path.join(d, src + ".s")
             r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
                                 "-I" + CSRC, "--cuda-device-only", "-S", os.path.join(CSRC, src), "-o", out],

@@ -92,7 +92,7 @@ def test_gemm_inner_scaled_symmetric(ctx, m):
     assert np.array_equal(bits(ctx.gemm_inner_scaled(r, s, r, s)), bits(ctx.gemm_inner(e, e)))
 
 
-@pytest.mark.parametrize("k,m", [(48, 8), (70, 8), (5, 16), (1, 1), (100, 3)])
+@pytest.mark.parametrize("k,m", [(48, 8), (70, 8), (5, 16), (1, 1), (100, 3), (70, 17)])
 @pytest.mark.parametrize("n", [N_SMALL, 2 * N_SMALL + 1])
 def test_gemm_outer_scaled(ctx, k, m, n):
     rng = np.random.default_rng(k * 10 + m)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of gemm_outer's lockstep source groups (csrc/kernels_panel.hip, default) against free-running
+"""A/B of gemm_outer's lockstep source groups (csrc/kernels_outer.hip, default) against free-running
 waves (SSP_OUTER_LOCKSTEP=0), alternating processes so that placement and clocks affect both alike:
 the read-modify-write 48 -> 8 (the bench's dominant kernel), the write-only 48 -> 8 (construct_solution),
 64 -> 16 and 1 -> 8 at N = 1e8, library HIP-event ledger, median of 7.
