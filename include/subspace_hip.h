@@ -180,6 +180,15 @@ int ssp_ledger_entry(ssp_ctx* ctx, int i, const char** name, long long* calls, d
  * answered from those sums (the bits the dot itself gives, no "dot" row) until any other call of the
  * context; foreign code that writes vector memory in between must take ssp_ctx_stream or call
  * ssp_synchronize first, as above, which also drops the sums.  SSP_OUTER_NORMS=0 at ssp_ctx_create: off.
+ * A second such call of the same kind (both ssp_gemm_outer over zero-filled destinations, or both
+ * ssp_gemm_outer_set) with the same n, k, m <= 8 and bit-identical alphas, whose operands share no byte with
+ * the first one's destinations and whose destinations share none with its sources, stays pending next to
+ * it (a zero fill that touches no operand of either does not launch them).  ssp_axpy(a, x, y) with x exactly
+ * destination j of the first and y exactly destination j of the second then costs no memory access at all,
+ * and ssp_dot(y, y, n) on a destination of the second launches both calls as one kernel: one ledger row of
+ * 2 calls and 8 n (2 k + 2 m) bytes, results bit for bit those of the separate launches.  Any other call
+ * launches the first by itself and goes on as described above.  SSP_OUTER_PAIR=0 at ssp_ctx_create: off (the
+ * second call launches the first).
  * SSP_DEFER_OUTER=0 in the environment at ssp_ctx_create: every gemm_outer is launched at once. */
 int ssp_fill(ssp_ctx* ctx, double alpha, double* x, size_t n);
 /* x[:] *= alpha                        reference ArrayHandlerIterable.h:54-57 */

@@ -391,15 +391,21 @@ bool LedgerScope::dispatch_events(hipStream_t stream, hipEvent_t* start, hipEven
   return true;
 }
 
+void LedgerScope::calls(int c) {
+  if (slot_ < 0) return;
+  ctx_->ledger[slot_].calls += c - calls_;
+  calls_ = c;
+}
+
 void LedgerScope::detail(const std::string& tag) {
   if (slot_ < 0 || !ctx_->ledger_detail) return;
   const std::string name = ctx_->ledger[slot_].name + " [" + tag + "]";
   auto& from = ctx_->ledger[slot_];
-  from.calls -= 1;
+  from.calls -= calls_;
   const double b = last_bytes_;
   from.bytes -= b;
   const int to = ledger_slot(ctx_, name.c_str());
-  ctx_->ledger[to].calls += 1;
+  ctx_->ledger[to].calls += calls_;
   ctx_->ledger[to].bytes += b;
   slot_ = to;
 }
@@ -510,6 +516,7 @@ int ssp_ctx_create(int device, ssp_ctx** out) {
   if (const char* df = std::getenv("SSP_DEFER_FILL")) ctx->defer_fill = std::atoi(df) != 0;
   if (const char* dout = std::getenv("SSP_DEFER_OUTER")) ctx->outer.defer = std::atoi(dout) != 0;
   if (const char* on = std::getenv("SSP_OUTER_NORMS")) ctx->outer.norms_on = std::atoi(on) != 0;
+  if (const char* pr = std::getenv("SSP_OUTER_PAIR")) ctx->outer.pair_on = std::atoi(pr) != 0;
   if (const char* ct = std::getenv("SSP_COMM_TIMEOUT_S")) {
     const double v = std::atof(ct);
     if (v > 0) ctx->comm_timeout_s = v;
@@ -539,6 +546,7 @@ int ssp_ctx_destroy(ssp_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   ctx->pending_fills.clear();  // nobody can read the vectors of a destroyed context
   ctx->outer.pending.discard();
+  ctx->outer.pair.discard();
   (void)ssp::p2p_detach(ctx);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->comm) ncclCommDestroy(ctx->comm);

@@ -4,8 +4,9 @@
 // streams 3*8*48 vectors.  Here every vector of the panel is read from HBM exactly once per call:
 //   gemm_outer  bytes = 8 N (k + 2 m)
 // Also the one home of the deferral protocol over ssp_ctx::outer (DESIGN.md "Deferred gemm_outer"): when a
-// call becomes a record (gemm_outer_impl), who may attach to it (outer_take_axpy), who launches it and as
-// which instance (flush_outer, outer_serve_dot), when the kept norms die and where the rank-local sums live.
+// call becomes a record (gemm_outer_impl) or the second record of a pair (pair_candidate), who may attach to
+// it (outer_take_axpy), who launches it and as which instance (flush_outer, outer_serve_dot), which fill
+// leaves it pending (outer_keeps_fill), when the kept norms die and where the rank-local sums live.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -287,9 +288,199 @@ __global__ __launch_bounds__(kBlock) void k_gemm_outer(const OuterArgs a) {
   }
 }
 
+// The launch of a pair of records (pending_outer.h OuterPair): both solution constructions of a step in one
+// pass.  The two records share k, m, n and the alphas (device-resident: 2 k pointers, 2 m destinations and the
+// alphas do not fit the argument block together; one staged upload of 8 k m bytes per launch, as every launch
+// with k m > kOuterAlpha makes).
+struct PairArgs {
+  const double* xp[ssp::kOuterSrc];  // A's sources
+  const double* xa[ssp::kOuterSrc];  // B's sources
+  double* yp[ssp::OuterPair::kDst];  // A's destinations
+  double* ya[ssp::OuterPair::kDst];  // B's destinations
+  double e[ssp::OuterPair::kDst];    // register terms: ya[j] += e[j] * yp[j] for the bits of mask
+  const double* alpha_dev;           // alpha[i * m + j]
+  size_t n;
+  int k;
+  int m;
+  int mask;
+  double* partial;  // as OuterArgs::partial, for the sums of squares of ya
+  ssp::FoldTail tail;
+};
+static_assert(sizeof(PairArgs) <= 4000, "kernel argument block too large");
+
+// yp[j] = sum_i alpha(i,j) xp[i]; ya[j] = sum_i alpha(i,j) xa[i], then for the masked j
+// ya[j] = fma(e[j], yp[j], ya[j]) with yp[j] the accumulator just stored -- the double the separate launch
+// would have reloaded, so the fma is k_axpy_win's (or EPI's) -- and the sums of squares of the stored ya[j].
+// Every destination sees its sources in the order i = 0..k-1 from +0.0, as the SET instance forms it; an
+// unmasked destination takes no fma, for the reasons given at k_gemm_outer.  Always the norm-carrying form
+// (the pair is launched by the ssp_dot of one of B's destinations and by nothing else), so it takes
+// k_dot_partial's grid and walk exactly as the NRM instance of k_gemm_outer does.  Two accumulator sets at
+// 4-position windows would need 256 VGPRs: a wave covers its window as two half-windows of two positions
+// (u = 0, 1, then u = 2, 3), the P sums then the A sums of each, and each half-window feeds the norm
+// accumulators of its own two positions, so accumulator u sees the elements it sees in k_dot_partial, in
+// that order.  B: sources in flight per phase.
+constexpr int kPairHalf = 2;
+template <int M, int B>
+__global__ __launch_bounds__(kBlock) void k_gemm_outer_pair(const PairArgs a) {
+  static_assert(M <= ssp::OuterPair::kDst && kOuterWin % kPairHalf == 0, "two half-windows of a dot window");
+  using ssp::ld2nt;
+  using ssp::st2nt;
+  using cdouble = const __attribute__((address_space(4))) double;
+  const auto alpha = [&](int idx) { return ((cdouble*)a.alpha_dev)[idx]; };
+  constexpr int U = kOuterWin, H = kPairHalf;
+  const int lane = threadIdx.x & 63;
+  const size_t gw = size_t(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
+  const size_t nw = size_t(gridDim.x) * (kBlock / 64);
+  const size_t n2 = a.n >> 1, win = 64 * U;
+  const double2 z2 = make_double2(0, 0);
+  double* nacc = outer_norm_acc<M>() + threadIdx.x;  // [j][u] at (j * U + u) * kBlock
+#pragma unroll
+  for (int q = 0; q < M * U; ++q) nacc[q * kBlock] = 0;
+  // acc[v][j] = sum_i alpha(i,j) x[i] at the positions q0 + 64 v
+  const auto sums = [&](const double* const(&x)[ssp::kOuterSrc], size_t q0, double2(&acc)[H][M]) {
+#pragma unroll
+    for (int v = 0; v < H; ++v)
+#pragma unroll
+      for (int j = 0; j < M; ++j) acc[v][j] = z2;
+    int i = 0;
+    for (; i + B <= a.k; i += B) {
+      double2 xv[B][H];
+#pragma unroll
+      for (int b = 0; b < B; ++b)
+#pragma unroll
+        for (int v = 0; v < H; ++v) xv[b][v] = ld2nt(x[i + b] + 2 * (q0 + 64 * v));
+#pragma unroll
+      for (int b = 0; b < B; ++b)
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+          if (j < a.m) {
+            const double al = alpha((i + b) * a.m + j);
+#pragma unroll
+            for (int v = 0; v < H; ++v) {
+              acc[v][j].x = fma(al, xv[b][v].x, acc[v][j].x);
+              acc[v][j].y = fma(al, xv[b][v].y, acc[v][j].y);
+            }
+          }
+        }
+    }
+    for (; i < a.k; ++i) {
+      double2 xv[H];
+#pragma unroll
+      for (int v = 0; v < H; ++v) xv[v] = ld2nt(x[i] + 2 * (q0 + 64 * v));
+#pragma unroll
+      for (int j = 0; j < M; ++j) {
+        if (j < a.m) {
+          const double al = alpha(i * a.m + j);
+#pragma unroll
+          for (int v = 0; v < H; ++v) {
+            acc[v][j].x = fma(al, xv[v].x, acc[v][j].x);
+            acc[v][j].y = fma(al, xv[v].y, acc[v][j].y);
+          }
+        }
+      }
+    }
+  };
+  for (size_t c = gw; c < n2 / win; c += nw) {  // whole windows only, as ssp::for_windows walks them
+#pragma unroll
+    for (int h = 0; h < U / H; ++h) {
+      const size_t q0 = c * win + 64 * H * h + lane;  // window position u = H h + v at q0 + 64 v
+      double2 ap[H][M], aa[H][M];
+      sums(a.xp, q0, ap);
+#pragma unroll
+      for (int v = 0; v < H; ++v)
+#pragma unroll
+        for (int j = 0; j < M; ++j)
+          if (j < a.m) st2nt(a.yp[j] + 2 * (q0 + 64 * v), ap[v][j]);
+      sums(a.xa, q0, aa);
+#pragma unroll
+      for (int j = 0; j < M; ++j)
+        if (j < a.m) {
+          if ((a.mask >> j) & 1) {
+            const double ea = a.e[j];
+#pragma unroll
+            for (int v = 0; v < H; ++v) {
+              aa[v][j].x = fma(ea, ap[v][j].x, aa[v][j].x);
+              aa[v][j].y = fma(ea, ap[v][j].y, aa[v][j].y);
+            }
+          }
+#pragma unroll
+          for (int v = 0; v < H; ++v) {
+            st2nt(a.ya[j] + 2 * (q0 + 64 * v), aa[v][j]);
+            double s = nacc[(j * U + H * h + v) * kBlock];
+            s = fma(aa[v][j].x, aa[v][j].x, s);
+            s = fma(aa[v][j].y, aa[v][j].y, s);
+            nacc[(j * U + H * h + v) * kBlock] = s;
+          }
+          // one destination's accumulators in registers at a time, as in the NRM instance of k_gemm_outer
+          __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+  }
+  if (blockIdx.x == 0) {
+    const size_t p = (n2 / win) * win + threadIdx.x;  // fewer than win = kBlock positions are left
+    if (p < n2) {
+      for (int j = 0; j < a.m; ++j) {
+        double2 vp = z2, va = z2;
+        for (int i = 0; i < a.k; ++i) {
+          const double al = alpha(i * a.m + j);
+          const double2 xp = ld2(a.xp[i] + 2 * p), xa = ld2(a.xa[i] + 2 * p);
+          vp.x = fma(al, xp.x, vp.x);
+          vp.y = fma(al, xp.y, vp.y);
+          va.x = fma(al, xa.x, va.x);
+          va.y = fma(al, xa.y, va.y);
+        }
+        if ((a.mask >> j) & 1) {
+          va.x = fma(a.e[j], vp.x, va.x);
+          va.y = fma(a.e[j], vp.y, va.y);
+        }
+        ssp::st2(a.yp[j] + 2 * p, vp);
+        ssp::st2(a.ya[j] + 2 * p, va);
+        double s = nacc[j * U * kBlock];
+        s = fma(va.x, va.x, s);
+        s = fma(va.y, va.y, s);
+        nacc[j * U * kBlock] = s;
+      }
+    }
+    if ((a.n & 1) && threadIdx.x == 0) {
+      const size_t e = a.n - 1;
+      for (int j = 0; j < a.m; ++j) {
+        double vp = 0.0, va = 0.0;
+        for (int i = 0; i < a.k; ++i) {
+          vp = fma(alpha(i * a.m + j), a.xp[i][e], vp);
+          va = fma(alpha(i * a.m + j), a.xa[i][e], va);
+        }
+        if ((a.mask >> j) & 1) va = fma(a.e[j], vp, va);
+        a.yp[j][e] = vp;
+        a.ya[j][e] = va;
+        nacc[j * U * kBlock] = fma(va, va, nacc[j * U * kBlock]);
+      }
+    }
+  }
+  __shared__ double red[kBlock / 64][M];
+#pragma unroll
+  for (int j = 0; j < M; ++j)
+    if (j < a.m) {
+      const double s0 = nacc[(j * U + 0) * kBlock], s1 = nacc[(j * U + 1) * kBlock];
+      const double s2 = nacc[(j * U + 2) * kBlock], s3 = nacc[(j * U + 3) * kBlock];
+      double v = (s0 + s1) + (s2 + s3);
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+      if (lane == 0) red[threadIdx.x >> 6][j] = v;
+    }
+  __syncthreads();
+  if (int(threadIdx.x) < a.m) {
+    double s = 0;  // block_sum256's order
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) s += red[w][threadIdx.x];
+    ssp::store_partial(a.partial + size_t(blockIdx.x) * a.m + threadIdx.x, s);
+  }
+  ssp::fold_tail<M>(a.partial, a.tail);
+}
+
 // The norm-carrying instances (NRM): the unscaled write-only form up to 8 destinations, with or without
 // the epilogue.  16 destinations run 2-position windows and would need 128 KiB of LDS: not built.
 constexpr int kOuterNormDst = 8;
+constexpr int kPairSrc = 4;  // sources in flight per phase of k_gemm_outer_pair
 unsigned outer_norm_grid(const ssp_ctx* ctx, size_t n) { return ssp::win_grid(ctx, n, ssp::kDotU, 8); }
 
 // The instantiated width for m destinations: the M of the kernel and of its ledger tag.
@@ -411,12 +602,71 @@ int launch_record(ssp_ctx* ctx, const ssp::PendingOuter::Record& r, const ssp::F
   return launch_outer(ctx, a);
 }
 
+// The launch of a pair (pending_outer.h OuterPair), always as its norm-carrying kernel: one event pair under the
+// row that carries the calls' own name, two calls, the bytes of both constructions.  The register terms read
+// nothing from memory, so they add no bytes.
+template <int M>
+void launch_pair_inst(ssp_ctx* ctx, unsigned grid, const PairArgs& a) {
+  SSP_LAUNCH((k_gemm_outer_pair<M, kPairSrc>), dim3(grid), dim3(kBlock), 0, ctx->stream, a);
+}
+
+int launch_pair(ssp_ctx* ctx, const ssp::PendingOuter::Record& ra, const ssp::PendingOuter::Record& rb, unsigned mask,
+                const double* e, const ssp::FoldTail& norms) {
+  ssp::LedgerScope ls(ctx, rb.set ? "gemm_outer_set" : "gemm_outer", 8.0 * rb.n * (2.0 * rb.k + 2.0 * rb.m));
+  ls.calls(2);
+  PairArgs a{};
+  a.k = rb.k;
+  a.m = rb.m;
+  a.n = rb.n;
+  a.mask = int(mask);
+  for (int i = 0; i < rb.k; ++i) {
+    a.xp[i] = ra.x[i];
+    a.xa[i] = rb.x[i];
+  }
+  int terms = 0;
+  for (int j = 0; j < rb.m; ++j) {
+    a.yp[j] = ra.y[j];
+    a.ya[j] = rb.y[j];
+    const bool on = (mask >> j) & 1u;
+    a.e[j] = on ? e[j] : 0.0;
+    terms += on;
+  }
+  void* p;
+  SSP_TRY(ssp::upload_small(ctx, rb.alpha, sizeof(double) * size_t(rb.k) * size_t(rb.m), &p));
+  a.alpha_dev = static_cast<const double*>(p);
+  SSP_TRY(ssp::flush_uploads(ctx));
+  a.partial = ctx->partial;
+  a.tail = norms;
+  ls.detail(ssp::shape_tag("pair", outer_inst(rb.m), 1, rb.k, rb.m, false) + " reg" + std::to_string(terms) + " nrm");
+  const unsigned grid = outer_norm_grid(ctx, rb.n);
+  switch (outer_inst(rb.m)) {
+    case 1: launch_pair_inst<1>(ctx, grid, a); break;
+    case 2: launch_pair_inst<2>(ctx, grid, a); break;
+    case 4: launch_pair_inst<4>(ctx, grid, a); break;
+    case 8: launch_pair_inst<8>(ctx, grid, a); break;
+    default: return ssp::set_error(SSP_ERR_ARG, "gemm_outer: a pair wider than its kernel");
+  }
+  SSP_TRY_HIP(hipGetLastError());
+  return SSP_OK;
+}
+
+// Breaks a pair (OuterPair::unpair): A is launched alone, as the single record it was, and B is left as the
+// single pending record with the register terms as its epilogue terms.
+int unpair_outer(ssp_ctx* ctx) {
+  ssp::DeferredOuter& d = ctx->outer;
+  int status = SSP_OK;
+  d.pair.unpair(d.pending, [&](const ssp::PendingOuter::Record& r) { status = launch_record(ctx, r); });
+  return status;
+}
+
 // The ssp_dot(y, y, n) that finds a pending record with y exactly one of its destinations, n its length and
 // the norm-carrying instance built for its width: launches the record as that instance and keeps the m sums
 // (one rank: their values, after one wait; ranks: the rank-local sums in norms_dev).  Else nothing happens.
 int launch_outer_norms(ssp_ctx* ctx, const double* y, size_t n) {
   ssp::DeferredOuter& d = ctx->outer;
   if (!d.norms_on || !d.pending.pending()) return SSP_OK;
+  // a pair: B's destinations (a dot on one of A's, or on anything else, is declined and un-pairs in flush_outer)
+  const bool paired = d.pair.paired();
   const ssp::PendingOuter::Record& r = d.pending.record();
   const int m = r.m;
   if (m > kOuterNormDst || n != r.n || std::find(r.y, r.y + m, y) == r.y + m) return SSP_OK;
@@ -436,7 +686,11 @@ int launch_outer_norms(ssp_ctx* ctx, const double* y, size_t n) {
     return plain != SSP_OK ? plain : status;
   }
   d.norms.keep(r.y, m, r.n);
-  d.pending.flush([&](const ssp::PendingOuter::Record& rec) { status = launch_record(ctx, rec, &tail); });
+  if (paired)
+    d.pair.flush(d.pending, [&](const ssp::PendingOuter::Record& ra, const ssp::PendingOuter::Record& rb, unsigned mask,
+                                const double* e) { status = launch_pair(ctx, ra, rb, mask, e, tail); });
+  else
+    d.pending.flush([&](const ssp::PendingOuter::Record& rec) { status = launch_record(ctx, rec, &tail); });
   if (status == SSP_OK && !ranks) {
     // one wait for all m sums, before anything else can reuse the host result buffer
     double v[ssp::kOuterDst];
@@ -455,9 +709,17 @@ int flush_outer(ssp_ctx* ctx) {
   DeferredOuter& d = ctx->outer;
   d.norms.forget();
   if (!d.pending.pending()) return SSP_OK;
-  int status = SSP_OK;
-  d.pending.flush([&](const PendingOuter::Record& r) { status = launch_record(ctx, r); });
+  int status = unpair_outer(ctx);  // A first, by itself; B is then the single record
+  d.pending.flush([&](const PendingOuter::Record& r) {
+    const int s = launch_record(ctx, r);
+    if (status == SSP_OK) status = s;
+  });
   return status;
+}
+
+bool outer_keeps_fill(const ssp_ctx* ctx, const void* p, size_t n) {
+  const DeferredOuter& d = ctx->outer;
+  return d.pair_on && d.pending.pending() && p && aligned16(p) && !d.pair.touches(d.pending, p, n);
 }
 
 int outer_take_axpy(ssp_ctx* ctx, double alpha, const double* x, double xs, double* y, double ys, size_t n,
@@ -469,6 +731,15 @@ int outer_take_axpy(ssp_ctx* ctx, double alpha, const double* x, double xs, doub
   // An unscaled axpy onto exactly one destination of the pending record becomes its epilogue term; x is
   // read by that launch, so its pending zero fills are stored first.  Any other axpy launches the record.
   const bool valid = n > 0 && x && y && aligned16(x) && aligned16(y);
+  if (d.pair.paired()) {
+    // A's destination j onto B's destination j: a register term of the pair (no pending zero fill overlaps a
+    // destination of A).  Any other axpy un-pairs and is then taken as it always was.
+    if (valid && xs == 1.0 && ys == 1.0 && d.pair.attach(d.pending, alpha, x, y, n)) {
+      *attached = true;
+      return SSP_OK;
+    }
+    SSP_TRY(unpair_outer(ctx));
+  }
   if (valid && xs == 1.0 && ys == 1.0 && d.pending.attach(alpha, x, y, n)) {
     *attached = true;
     return flush_fills_over(ctx, x, n);
@@ -498,9 +769,38 @@ int outer_serve_dot(ssp_ctx* ctx, const double* x, double xs, const double* y, d
 }  // namespace ssp
 
 namespace {
+// The call would be recorded (below), and may stand as record B next to the single pending record A
+// (OuterPair::may_pair): every argument check of gemm_outer_impl passes, its operands are unscaled and outside
+// exact mode, and the read-modify-write form will consume the pending zero fills of all its destinations.
+bool pair_candidate(ssp_ctx* ctx, const double* alphas, const double* const* xx, const double* xs, int k,
+                    double* const* yy, const double* ys, int m, size_t n, bool set) {
+  ssp::DeferredOuter& d = ctx->outer;
+  if (!d.pair_on || !d.defer || !d.pending.pending()) return false;
+  if (d.pair.paired()) {  // a third call: A is launched, and the call is weighed against B alone
+    if (unpair_outer(ctx) != SSP_OK) return false;
+  }
+  if (!alphas || !xx || !yy || n == 0 || !ssp::PendingOuter::one_launch(k, m)) return false;
+  if (ssp::any_scaled(xs, k) || ssp::exact_mode(ctx, n)) return false;
+  for (int i = 0; i < k; ++i)
+    if (!xx[i] || !ssp::aligned16(xx[i])) return false;
+  for (int j = 0; j < m; ++j) {
+    if (!yy[j] || !ssp::aligned16(yy[j])) return false;
+    for (int i = 0; i < k; ++i)
+      if (yy[j] == xx[i]) return false;
+    if (!set && ctx->pending_fills.find_exact(yy[j], n) < 0) return false;
+  }
+  if (!set && ssp::any_scaled(ys, m)) return false;
+  return d.pair.may_pair(d.pending, alphas, xx, k, yy, m, n, set);
+}
+
 int gemm_outer_impl(ssp_ctx* ctx, const double* alphas, const double* const* xx, const double* xs, int k,
                     double* const* yy, const double* ys, int m, size_t n, bool set) {
-  SSP_CHECK_CTX_KEEP_FILLS(ctx);
+  if (!ctx) return ssp::set_error(SSP_ERR_ARG, "null ssp_ctx");
+  SSP_TRY(ssp::use_device(ctx));
+  // A call that will stand next to the pending record as the second of a pair (pair_candidate) leaves it
+  // pending; every other call launches it first, as SSP_CHECK_CTX_KEEP_FILLS does.
+  const bool try_pair = pair_candidate(ctx, alphas, xx, xs, k, yy, ys, m, n, set);
+  if (!try_pair) SSP_TRY(ssp::flush_outer(ctx));
   if (m < 0 || k < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_gemm_outer: negative dimension");
   if (set && k == 0) {
     // These zero fills may stay deferred past the return, like a caller's own ssp_fill(0): the next
@@ -552,6 +852,10 @@ int gemm_outer_impl(ssp_ctx* ctx, const double* alphas, const double* const* xx,
   // launched, so that the ssp_axpy calls that follow on its destinations ride on its stores; whatever
   // else comes next launches it first (ssp::flush_outer, under this call's ledger row).  Everything
   // above has happened as for the launch, so no pending zero fill overlaps an operand of the record.
+  if (try_pair) {
+    if (set0 && ctx->outer.pair.pair(ctx->outer.pending, alphas, xx, k, yy, m, n, set)) return SSP_OK;
+    SSP_TRY(ssp::flush_outer(ctx));  // pair_candidate has checked all of it: not reached
+  }
   if (ctx->outer.defer && set0 && !ssp::any_scaled(xs, k) && !ssp::exact_mode(ctx, n) &&
       ctx->outer.pending.record(alphas, xx, k, yy, m, n, set))
     return SSP_OK;

@@ -379,11 +379,15 @@ int overwrite_fills(ssp_ctx* ctx, const void* p, size_t n) {
 extern "C" {
 
 int ssp_fill(ssp_ctx* ctx, double alpha, double* x, size_t n) {
-  SSP_CHECK_CTX_KEEP_FILLS(ctx);
+  SSP_CHECK_CTX_KEEP_ALL(ctx);
   // A fill with +0.0 of a vector outside exact mode is recorded, not launched (pending_fill.h): the
   // next entry point stores it, unless it is one that overwrites or consumes it.  -0.0 and short
   // vectors keep the eager launch (fill_now validates x for that path).
-  if (ctx->defer_fill && n > 0 && alpha == 0.0 && !std::signbit(alpha) && !ssp::exact_mode(ctx, n)) {
+  const bool defer = ctx->defer_fill && n > 0 && alpha == 0.0 && !std::signbit(alpha) && !ssp::exact_mode(ctx, n);
+  // A recorded fill that touches no operand of a pending gemm_outer leaves it pending (outer_keeps_fill);
+  // every other fill launches it first.
+  if (!(defer && ssp::outer_keeps_fill(ctx, x, n))) SSP_TRY(ssp::flush_outer(ctx));
+  if (defer) {
     SSP_TRY(ssp::check_vec(x, n, "ssp_fill"));
     ssp::FillFlusher f{ctx};
     ctx->pending_fills.insert(x, n, f);

@@ -39,9 +39,15 @@ struct P2PComm;  // comm_p2p.hip
 // and the dots of the other destinations are answered from here; norms_on, SSP_OUTER_NORMS=0: off, every dot
 // runs k_dot_partial (the same-build A/B, and the switch case of tests/test_outer_norms_gpu.py).  norms_dev:
 // the rank-local sums when a rank transport is attached (each served dot reduces its own over the ranks).
+// pair: the older record of two pending ones, while `pending` holds the newer (pending_outer.h OuterPair): the two
+// solution constructions of a step, launched as one k_gemm_outer_pair by the ssp_dot of a destination of the
+// newer; pair_on, SSP_OUTER_PAIR=0: the second call launches the first, as it always did (the same-build A/B,
+// and the switch case of tests/test_outer_pair_gpu.py).
 struct DeferredOuter {
   bool defer = true;
   PendingOuter pending;
+  bool pair_on = true;
+  OuterPair pair;
   bool norms_on = true;
   OuterNorms norms;
   double* norms_dev = nullptr;
@@ -196,6 +202,10 @@ int outer_take_axpy(ssp_ctx* ctx, double alpha, const double* x, double xs, doub
 // attached.  Every other dot is declined, nothing launched or forgotten: the caller takes the default prologue.
 int outer_serve_dot(ssp_ctx* ctx, const double* x, double xs, const double* y, double ys, size_t n, double* out,
                     bool* served);
+// ssp_fill's question before its prologue: a record is pending and the deferred zero fill of [p, p + 8 n) shares
+// no byte with a source, a destination or an epilogue source of a pending record, so the records stay pending
+// (the zero fills between the two gemm_outers of a step must not break their pair).  Never with SSP_OUTER_PAIR=0.
+bool outer_keeps_fill(const ssp_ctx* ctx, const void* p, size_t n);
 // use_device, then flush_outer and flush_fills.
 int enter(ssp_ctx* ctx);
 int ensure_partial(ssp_ctx* ctx, size_t n_doubles);
@@ -282,6 +292,8 @@ class LedgerScope {
   // SSP_LEDGER_DETAIL (read at context creation): the op's call and bytes move to the entry
   // "<op> [tag]" -- per-instance ledger rows (kernel shape) for the development tools
   void detail(const std::string& tag);
+  // the scope stands for c calls of the op (one launch for both gemm_outers of a pair); before detail()
+  void calls(int c);
   // dispatch timing: the events for the next kernel launched on this thread inside an open scope, when
   // it is launched on that scope's context stream
   static bool dispatch_events(hipStream_t stream, hipEvent_t* start, hipEvent_t* stop);
@@ -293,6 +305,7 @@ class LedgerScope {
   hipEvent_t stop_ = nullptr;  // dispatch timing
   bool launched_ = false;
   double last_bytes_ = 0;
+  int calls_ = 1;
   LedgerScope* prev_ = nullptr;
 };
 
@@ -578,8 +591,9 @@ int launch_reduce_partials(ssp_ctx* ctx, const double* partial, int nblocks, int
   } while (0)
 
 // The same with the zero fills left pending (the pending gemm_outer is launched), for the entry points
-// that look at the table themselves: ssp_fill, ssp_gemm_outer*, ssp_copy, ssp_scal_copy, ssp_rows_* and
-// ssp_free.
+// that look at the table themselves: ssp_copy, ssp_scal_copy, ssp_rows_* and ssp_free.  ssp_fill and
+// ssp_gemm_outer* do the same by hand, except for the fill and the call that leave the records pending
+// (outer_keeps_fill; pair_candidate in kernels_outer.hip).
 #define SSP_CHECK_CTX_KEEP_FILLS(ctx)                                   \
   do {                                                                  \
     if (!(ctx)) return ssp::set_error(SSP_ERR_ARG, "null ssp_ctx");     \
@@ -587,7 +601,8 @@ int launch_reduce_partials(ssp_ctx* ctx, const double* partial, int nblocks, int
     SSP_TRY(ssp::flush_outer(ctx));                                     \
   } while (0)
 
-// Device only: ssp_axpy, which may attach to the pending gemm_outer instead of launching it.
+// Device only: ssp_axpy and ssp_dot, which may attach to the pending gemm_outer or be served by its launch, and
+// ssp_fill, which may leave it pending.
 #define SSP_CHECK_CTX_KEEP_ALL(ctx)                                     \
   do {                                                                  \
     if (!(ctx)) return ssp::set_error(SSP_ERR_ARG, "null ssp_ctx");     \
