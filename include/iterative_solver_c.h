@@ -195,13 +195,24 @@ void IterativeSolverHbmDiagonalsDevice(double* diagonals);
  *                   the plain solver, a rebuild in every iteration once the Q space is full.  With a limit under
  *                   about 8 nroot the mode may stall short of an f64 threshold (near 1e-10 |H|).
  * Refused, each with an error that names the option (recorded, not thrown, after IterativeSolverHbmSetThrow(0)):
- * an unknown Q_STORAGE value; either option on NonLinearEquations, Optimize or RSPT; either
- * option on an instance with more than one rank; Q_REFINE with hermitian = 0, MAX_SIZE_QSPACE, RESET_D or
+ * an unknown Q_STORAGE value; either option on Optimize or RSPT, Q_REFINE on NonLinearEquations (Q_STORAGE=f32
+ * there: below); either option on an instance with more than one rank; Q_REFINE with hermitian = 0, MAX_SIZE_QSPACE, RESET_D or
  * RESET_D_MAX_Q_SIZE (the refined mode has no D space); Q_STORAGE=f32 over a vector library without the
  * mixed-precision ABI.  Out of scope: multi-rank f32 instances, a D space or a Q-space limit in refined mode
  * without Q_REFINE_DSPACE=1, the D-space reset in refined mode,
- * f32 Q for DIIS and the optimisers, a Fortran binding of the refine callback (the Fortran module passes
+ * f32 Q for the optimisers (BFGS, SD), a Fortran binding of the refine callback (the Fortran module passes
  * `options` through, so the plain Q_STORAGE=f32 works from Fortran), a device-side apply_on_p.
+ *
+ * Non-linear equations.  IterativeSolverNonLinearEquationsInitialize accepts Q_STORAGE=f32 (one rank, "DIIS"): the
+ * instance's solver is NonLinearEquationsDIISDifferences (itsolv_hbm/diis_differences.h), whose history is two f64
+ * anchors (the newest parameters and residual) and, for every older point, an f32 pair of differences between
+ * successive iterates -- (k - 1) 8 n + 16 n bytes for k points where the f64 instance holds 16 k n.  The
+ * differences shrink with the error, so f64 thresholds are reached in the f64 instance's iterations with no
+ * further residual evaluation: there is no refined mode to turn on, and Q_REFINE stays refused.  The calls, their
+ * host and device forms, MAX_SIZE_QSPACE, SVD_THRESH and the statistics are the f64 instance's;
+ * IterativeSolverHbmQStorage reports 4.  Refused by name: an algorithm other than "DIIS", an instance with more
+ * than one rank, a P space (IterativeSolverAddP), and Q_STORAGE=f32 over a vector library without the
+ * mixed-precision ABI.
  *
  * Linear equations.  IterativeSolverLinearEquationsInitialize accepts Q_STORAGE=f32 and, with it, Q_REFINE=1 and
  * Q_REFINE_KAPPA (one rank, "Davidson").  Plain: the right-hand sides are stored rounded with the Q space, so the

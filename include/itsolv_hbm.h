@@ -215,6 +215,26 @@ int itsolv_optimize_dense(ssp_ctx* ctx, const double* h, size_t n, int algorithm
                           itsolv_result* out, double* x_out);
 int itsolv_diis_dense(ssp_ctx* ctx, const double* h, size_t n, const itsolv_options* opt, itsolv_result* out,
                       double* x_out);
+/* DIIS with its history in f32 (itsolv_hbm/diis_differences.h: NonLinearEquationsDIISDifferences<Vec, VecF32,
+ * SparseP> over make_handlers_q32()), the problems, options and result of itsolv_diis_synth / itsolv_diis_dense.
+ * The history is not k rounded (parameter, residual) pairs -- rounding every iterate leaves the residual stuck near
+ * 2^-24 |J| |x*| -- but two f64 anchors (the newest pair) and k - 1 pairs of f32 differences between successive
+ * iterates, each rounded once: what the rounding loses shrinks with the error, so f64 thresholds are reached in
+ * the iterations of the f64 solve, with no extra residual evaluation and no mode flag.  A history of k pairs
+ * takes (k - 1) 8 n + 16 n bytes where the f64 solve takes 16 k n.  A new pair is taken in by one
+ * ssp_q32_store_differences, the new row of the DIIS matrix is one ssp_q32_gemm_inner_cols (r_0 against itself
+ * and the k - 1 residual differences), and both constructions of a step are one ssp_q32_anchor_combine.
+ * max_size_qspace and the svd pruning act as in the f64 solve.  Refused, the message naming it: max_p > 0 (a P
+ * space), and a context with more than one rank. */
+int itsolv_diis_synth_q32(ssp_ctx* ctx, size_t n, const sspx_synth* spec, const itsolv_options* opt, itsolv_result* out,
+                          double* x_out);
+int itsolv_diis_dense_q32(ssp_ctx* ctx, const double* h, size_t n, const itsolv_options* opt, itsolv_result* out,
+                          double* x_out);
+/* What the last itsolv_diis_*_q32 solve of this thread held when it ended: the points of its history, the pairs
+ * of f32 differences among them (points - 1), and the bytes of the context's arena in use by the history (the
+ * anchors and the differences; from ssp_memory_stats around the solver's life).  Any pointer may be NULL.
+ * Returns 0. */
+int itsolv_q32_diis_stats(int* points, int* pairs, size_t* history_bytes);
 
 #ifdef __cplusplus
 }

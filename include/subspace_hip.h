@@ -453,6 +453,34 @@ int ssp_q32_block_update(ssp_ctx* ctx, const double* palphas, const size_t* ptr,
  * writes zeros; m = 0 and n = 0 return at once.  Ledger name combine_widen_f32, bytes n (4 k + 12 m). */
 int ssp_q32_combine_widen(ssp_ctx* ctx, const double* alphas, const float* const* xx, int k, float* const* yy,
                           double* const* ww, int m, size_t n);
+/* A DIIS history stored as differences (itsolv_hbm/diis_differences.h): the newest point of each of m series
+ * (the parameters and the residuals) is kept in f64 (the anchor aa[j]), every older point as the f32 difference
+ * between it and its successor.  A new point vv[j] is taken in by one pass:
+ *   dd[j][:] = (float)(vv[j][:] - aa[j][:])   subtracted in f64 (one rounding), narrowed to nearest-even
+ *   aa[j][:] = vv[j][:]
+ * 28 bytes per element and vector, where ssp_copy to scratch, ssp_axpy(-1), ssp_mx_copy (F32 <- F64) and
+ * ssp_copy to the anchor move 68; bit-identical to that sequence at every length and exact_max (each element
+ * is one subtraction and one narrowing in either arithmetic).  dd null: aa[j] = vv[j] only (the first point).
+ *   - Pending zero fills of vv and aa are stored, those of dd dropped.  Pointers 16-byte aligned; no aa[j] or
+ *     dd[j] may be a vv[l], another aa[l] or dd[l] (SSP_ERR_ARG); m = 0 and n = 0 return at once.  One launch
+ *     per 16 vectors.  No reduction: nothing is exchanged between ranks.
+ * Ledger name store_differences_f32, bytes 28 n m. */
+int ssp_q32_store_differences(ssp_ctx* ctx, const double* const* vv, double* const* aa, float* const* dd, int m,
+                              size_t n);
+/* Combinations of such series, m panels that share one coefficient vector (the parameter and the residual
+ * construction of a DIIS step in one launch; m = 1: the parameters alone):
+ *   yy[j][:] = aa[j][:] - sum_i gammas[i] (double)dd[j*k + i][:]     j < m, i < k
+ * as y = a, then y = fma(-gammas[i], d_i, y) for i = 0..k-1: bit-identical to ssp_copy(yy[j], aa[j]) followed
+ * by ssp_mx_gemm_outer(alphas = -gammas, dd + j k, F32 -> yy[j], F64, set = 0), on vectors of at most exact_max
+ * elements too (there the pass is that sequence, on the exact path).  The destinations are written, not read:
+ * n m (16 + 4 k) bytes, where the sequence moves n m (40 + 4 k).  k = 0 copies the anchors.
+ *   - Two panels per launch, 64 differences per launch (more chain: each later launch goes on from what the one
+ *     before stored, the same fma chain).  Pending zero fills of aa and dd are stored, those of yy dropped.
+ *     Pointers 16-byte aligned; no yy[j] may be an aa[l], a dd[i] or another yy[l] (SSP_ERR_ARG); m = 0 and
+ *     n = 0 return at once.  No reduction: nothing is exchanged between ranks.
+ * Ledger name anchor_combine_f32, bytes n m (16 + 4 k). */
+int ssp_q32_anchor_combine(ssp_ctx* ctx, const double* gammas, const double* const* aa, const float* const* dd, int k,
+                           double* const* yy, int m, size_t n);
 
 /* ---- selection: reference util/select.h:28-55, util/select_max_dot.h:166-190,
  *      DistrArray.cpp:170-276.  Local shard [offset, offset+n) of a global array.  Returns up

@@ -15,7 +15,9 @@
 // k_mx_rhs_residual_norms<TB, K> (y_j = s_j (ys_j y_j - b_j) with b stored as TB, and <y_j, y_j>, up to 16 pairs per launch);
 // k_quantise_f32 (f64 vectors rounded through f32 in place, up to 16 per launch); k_mx_fill; k_mx_outer<TX, TY, M, SET, TWIN> (gemm_outer, launched chunk by chunk from outer_chunks, also the
 // dense pass of the ssp_q32_* updates; TWIN: ssp_q32_combine_widen's second store of every result, widened); k_mx_inner<TX, CP, MG, NG> (gemm_inner: the one MFMA tile kernel,
-// CP the columns' storage -- float, double, or ByGroup for ssp_q32_gemm_inner_cols).  with_pair maps the
+// CP the columns' storage -- float, double, or ByGroup for ssp_q32_gemm_inner_cols); k_q32_store_diff and
+// k_q32_anchor_combine (a DIIS history stored as f32 differences behind f64 anchors: for_quads' windows, and
+// k_mx_outer's window with one destination that starts from its anchor).  with_pair maps the
 // storage pair of a call to the kernel's types.
 #include <algorithm>
 #include <cstddef>
@@ -573,6 +575,132 @@ __global__ __launch_bounds__(kBlock) void k_mx_inner(const MxInnerArgs a) {
     }
   }
   ssp::tile_store_partials<MG, NG>(acc, a.m, a.k, a.partial);
+}
+
+// ---- a DIIS history stored as differences (ssp_q32_store_differences, ssp_q32_anchor_combine) ------
+struct StoreDiffArgs {
+  const double* v[ssp::kPrecVec];
+  double* a[ssp::kPrecVec];
+  float* d[ssp::kPrecVec];
+  size_t n;
+};
+
+// The lane's U quads p0 + 64 u of one vector: the quads of v and of a are all in flight before the first
+// difference is formed; d takes (float)(v - a), the subtraction rounded once, and a takes v.
+template <int U, bool NT>
+__device__ __forceinline__ void store_diff_at(const double* v, double* a, float* d, size_t p0) {
+  Raw<double> vv[U], av[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) vv[u] = ldq<NT>(v + 4 * (p0 + 64 * u));
+#pragma unroll
+  for (int u = 0; u < U; ++u) av[u] = ldq<NT>(static_cast<const double*>(a) + 4 * (p0 + 64 * u));
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    double x[4], w[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      x[e] = vv[u].get(e);
+      w[e] = x[e] - av[u].get(e);
+    }
+    stq<NT>(d + 4 * (p0 + 64 * u), w);
+    stq<NT>(a + 4 * (p0 + 64 * u), x);
+  }
+}
+
+// d[j] = (float)(v[j] - a[j]), then a[j] = v[j], vector j = blockIdx.y, over the windows of for_quads (the f32
+// and f64 elements of a position meet in one lane): 8 + 8 bytes read and 4 + 8 written per element.  The same
+// kernel at every length: each element is one subtraction and one narrowing, whatever arithmetic forms it.
+__global__ __launch_bounds__(kBlock) void k_q32_store_diff(const StoreDiffArgs a) {
+  const double* const v = a.v[blockIdx.y];
+  double* const an = a.a[blockIdx.y];
+  float* const d = a.d[blockIdx.y];
+  for_quads<kMxU>(
+      a.n, [&](size_t p0) { store_diff_at<kMxU, true>(v, an, d, p0); },
+      [&](size_t p) { store_diff_at<1, false>(v, an, d, p); },
+      [&](size_t i) {
+        const double x = v[i];
+        d[i] = float(x - an[i]);
+        an[i] = x;
+      });
+}
+
+constexpr int kAnchorPanels = 2;  // panels per ssp_q32_anchor_combine launch: the parameters and the residuals
+struct AnchorCombineArgs {
+  const double* a[kAnchorPanels];  // what a panel starts from: its anchor, or y itself from the second source chunk on
+  double* y[kAnchorPanels];
+  const float* d[kAnchorPanels][ssp::kOuterSrc];
+  double g[ssp::kOuterSrc];  // -gamma_i
+  int k;
+  size_t n;
+};
+
+// y_j = a_j - sum_i gamma_i (double)d_j,i for panel j = blockIdx.y: k_mx_outer's window (2 x 64 quads per wave,
+// batches of 8 f32 sources in flight before their fmas) with one destination, whose accumulator starts from the
+// anchor instead of the destination: acc = a, then acc = fma(-gamma_i, d_i, acc) for i = 0..k-1 -- the chain of
+// k_mx_outer<float, double, 1, false> on a copy of a, element for element.  Coefficients and source pointers
+// are wave-uniform reads through the constant address space.
+__global__ __launch_bounds__(kBlock) void k_q32_anchor_combine(const AnchorCombineArgs a) {
+  using cchar = const __attribute__((address_space(4))) char;
+  using cdouble = const __attribute__((address_space(4))) double;
+  typedef const float* cfloatp;
+  cchar* const karg = (cchar*)__builtin_amdgcn_kernarg_segment_ptr();
+  const int j = blockIdx.y;
+  cdouble* const g = (cdouble*)(karg + offsetof(AnchorCombineArgs, g));
+  const __attribute__((address_space(4))) cfloatp* const d =
+      (const __attribute__((address_space(4))) cfloatp*)(karg + offsetof(AnchorCombineArgs, d)) + j * ssp::kOuterSrc;
+  const double* const src = a.a[j];
+  double* const y = a.y[j];
+  constexpr int U = 2, B = 8;
+  const int lane = threadIdx.x & 63;
+  const size_t gw = size_t(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
+  const size_t nw = size_t(gridDim.x) * (kBlock / 64);
+  const size_t n4 = a.n >> 2, win = 64 * U;
+  for (size_t c = gw; c * win < n4; c += nw) {
+    const size_t p0 = c * win + lane;
+    bool ok[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) ok[u] = p0 + 64 * u < n4;
+    double acc[U][4];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const Raw<double> r = ok[u] ? ldq<true>(src + 4 * (p0 + 64 * u)) : zero_quad<double>();
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[u][e] = r.get(e);
+    }
+    const auto add = [&](int i, const Raw<float>(&xv)[U]) {
+      const double gi = g[i];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[u][e] = fma(gi, xv[u].get(e), acc[u][e]);
+    };
+    int i = 0;
+    for (; i + B <= a.k; i += B) {
+      Raw<float> xv[B][U];
+#pragma unroll
+      for (int b = 0; b < B; ++b)
+#pragma unroll
+        for (int u = 0; u < U; ++u) xv[b][u] = ok[u] ? ldq<true>(d[i + b] + 4 * (p0 + 64 * u)) : zero_quad<float>();
+#pragma unroll
+      for (int b = 0; b < B; ++b) add(i + b, xv[b]);
+    }
+    for (; i < a.k; ++i) {
+      Raw<float> xv[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) xv[u] = ok[u] ? ldq<true>(d[i] + 4 * (p0 + 64 * u)) : zero_quad<float>();
+      add(i, xv);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (ok[u]) stq<true>(y + 4 * (p0 + 64 * u), acc[u]);
+  }
+  // the n mod 4 last elements: one thread of workgroup 0 each
+  if (blockIdx.x == 0 && threadIdx.x < (a.n & 3)) {
+    const size_t e = 4 * n4 + threadIdx.x;
+    double v = src[e];
+    for (int i = 0; i < a.k; ++i) v = fma(g[i], double(d[i][e]), v);
+    y[e] = v;
+  }
 }
 
 // ---- host side ------------------------------------------------------------------------------------
@@ -1252,6 +1380,114 @@ int ssp_mx_gemm_outer(ssp_ctx* ctx, const double* alphas, const void* const* xx,
   bool scaled = false;
   for (int i = 0; xs && i < k; ++i) scaled = scaled || xs[i] != 1.0;
   return outer_chunks(ctx, alphas, xx, tx, scaled ? xs : nullptr, k, yy, ty, nullptr, m, n, set != 0);
+}
+
+int ssp_q32_store_differences(ssp_ctx* ctx, const double* const* vv, double* const* aa, float* const* dd, int m,
+                              size_t n) {
+  SSP_CHECK_CTX_KEEP_FILLS(ctx);
+  if (m < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_q32_store_differences: negative dimension");
+  if (m == 0 || n == 0) return SSP_OK;
+  SSP_TRY(ssp::check_ptrs(vv, m, n, "ssp_q32_store_differences"));
+  SSP_TRY(ssp::check_ptrs(aa, m, n, "ssp_q32_store_differences"));
+  if (dd) SSP_TRY(ssp::check_ptrs(dd, m, n, "ssp_q32_store_differences"));
+  for (int j = 0; j < m; ++j)
+    for (int l = 0; l < m; ++l) {
+      const void* const d = dd ? static_cast<const void*>(dd[l]) : nullptr;
+      if (aa[j] == vv[l] || (dd && (d == vv[j] || d == aa[j])))
+        return ssp::set_error(SSP_ERR_ARG, "ssp_q32_store_differences: a destination aliases a source");
+      if (l != j && (aa[l] == aa[j] || (dd && dd[l] == dd[j])))
+        return ssp::set_error(SSP_ERR_ARG, "ssp_q32_store_differences: two destinations are the same vector");
+    }
+  if (!dd) {  // the first point: the anchors only (ssp_copy drops their pending zero fills and stores the sources')
+    for (int j = 0; j < m; ++j) SSP_TRY(ssp_copy(ctx, aa[j], vv[j], n));
+    return SSP_OK;
+  }
+  // pending zero fills: the new points and the anchors are read; the differences are written in full and read by
+  // nothing (one that only shares bytes with a difference's odd end is stored first)
+  if (!ctx->pending_fills.empty())
+    for (int j = 0; j < m; ++j) {
+      SSP_TRY(ssp::flush_fills_over(ctx, vv[j], n));
+      SSP_TRY(ssp::flush_fills_over(ctx, aa[j], n));
+      SSP_TRY(ssp::overwrite_fills(ctx, dd[j], n / 2));
+      SSP_TRY(ssp::flush_fills_over(ctx, dd[j], (n + 1) / 2));
+    }
+  ssp::LedgerScope ls(ctx, "store_differences_f32", 28.0 * m * n);
+  for (int v0 = 0; v0 < m; v0 += ssp::kPrecVec) {
+    StoreDiffArgs a{};
+    const int mm = std::min(ssp::kPrecVec, m - v0);
+    for (int v = 0; v < mm; ++v) {
+      a.v[v] = vv[v0 + v];
+      a.a[v] = aa[v0 + v];
+      a.d[v] = dd[v0 + v];
+    }
+    a.n = n;
+    SSP_LAUNCH(k_q32_store_diff, dim3(quad_grid(ctx, n, kMxU, 16), unsigned(mm)), dim3(kBlock), 0, ctx->stream, a);
+    SSP_TRY_HIP(hipGetLastError());
+  }
+  return SSP_OK;
+}
+
+int ssp_q32_anchor_combine(ssp_ctx* ctx, const double* gammas, const double* const* aa, const float* const* dd, int k,
+                           double* const* yy, int m, size_t n) {
+  SSP_CHECK_CTX_KEEP_FILLS(ctx);
+  if (m < 0 || k < 0) return ssp::set_error(SSP_ERR_ARG, "ssp_q32_anchor_combine: negative dimension");
+  if (m == 0 || n == 0) return SSP_OK;
+  SSP_TRY(ssp::check_ptrs(aa, m, n, "ssp_q32_anchor_combine"));
+  SSP_TRY(ssp::check_ptrs(yy, m, n, "ssp_q32_anchor_combine"));
+  SSP_TRY(ssp::check_ptrs(dd, m * k, n, "ssp_q32_anchor_combine"));
+  if (k > 0 && !gammas) return ssp::set_error(SSP_ERR_ARG, "ssp_q32_anchor_combine: null gammas");
+  for (int j = 0; j < m; ++j) {
+    for (int l = 0; l < m; ++l) {
+      if (yy[j] == aa[l]) return ssp::set_error(SSP_ERR_ARG, "ssp_q32_anchor_combine: a destination aliases a source");
+      if (l != j && yy[l] == yy[j])
+        return ssp::set_error(SSP_ERR_ARG, "ssp_q32_anchor_combine: two destinations are the same vector");
+    }
+    for (int i = 0; i < m * k; ++i)
+      if (static_cast<const void*>(yy[j]) == dd[i])
+        return ssp::set_error(SSP_ERR_ARG, "ssp_q32_anchor_combine: a destination aliases a source");
+  }
+  // pending zero fills: the anchors and the differences are read; the destinations are written in full and read
+  // by nothing, so theirs are dropped
+  if (!ctx->pending_fills.empty()) {
+    for (int j = 0; j < m; ++j) SSP_TRY(ssp::flush_fills_over(ctx, aa[j], n));
+    for (int i = 0; i < m * k; ++i) SSP_TRY(ssp::flush_fills_over(ctx, dd[i], (n + 1) / 2));
+    for (int j = 0; j < m; ++j) SSP_TRY(ssp::overwrite_fills(ctx, yy[j], n));
+  }
+  if (k == 0) {  // no differences: the anchors themselves
+    for (int j = 0; j < m; ++j) SSP_TRY(ssp_copy(ctx, yy[j], aa[j], n));
+    return SSP_OK;
+  }
+  std::vector<double> neg(static_cast<size_t>(k));
+  for (int i = 0; i < k; ++i) neg[size_t(i)] = -gammas[i];
+  if (ssp::exact_mode(ctx, n)) {  // short vectors: the unfused sequence itself, ssp_mx_gemm_outer's exact path
+    for (int j = 0; j < m; ++j) {
+      SSP_TRY(ssp_copy(ctx, yy[j], aa[j], n));
+      void* y = yy[j];
+      SSP_TRY(ssp_mx_gemm_outer(ctx, neg.data(), reinterpret_cast<const void* const*>(dd + size_t(j) * k), SSP_F32,
+                                nullptr, k, &y, SSP_F64, 1, n, 0));
+    }
+    return SSP_OK;
+  }
+  ssp::LedgerScope ls(ctx, "anchor_combine_f32", (16.0 + 4.0 * k) * m * n);
+  // one wave per window of 2 x 64 quads, ctx->outer_per_cu workgroups per CU: outer_chunks' grid
+  const unsigned grid = ssp::stream_grid(ctx, n / 4 + 1, 2, unsigned(ctx->outer_per_cu));
+  for (int j0 = 0; j0 < m; j0 += kAnchorPanels) {
+    const int mm = std::min(kAnchorPanels, m - j0);
+    for (int i0 = 0; i0 < k; i0 += ssp::kOuterSrc) {  // later source chunks go on from what the one before stored
+      AnchorCombineArgs a{};
+      a.k = std::min(ssp::kOuterSrc, k - i0);
+      a.n = n;
+      for (int i = 0; i < a.k; ++i) a.g[i] = neg[size_t(i0 + i)];
+      for (int j = 0; j < mm; ++j) {
+        a.a[j] = i0 == 0 ? aa[j0 + j] : yy[j0 + j];
+        a.y[j] = yy[j0 + j];
+        for (int i = 0; i < a.k; ++i) a.d[j][i] = dd[size_t(j0 + j) * k + i0 + i];
+      }
+      SSP_LAUNCH(k_q32_anchor_combine, dim3(grid, unsigned(mm)), dim3(kBlock), 0, ctx->stream, a);
+      SSP_TRY_HIP(hipGetLastError());
+    }
+  }
+  return SSP_OK;
 }
 
 }  // extern "C"

@@ -43,6 +43,7 @@ const auto rows_export_fn = &ssp_rows_export;
 const auto rows_export_q_fn = &ssp_rows_export_quantised;
 const auto make_q32_fn = &itsolv_rc::make_rc_davidson_q32;  // null without host_q32/ (rc_solver.h)
 const auto make_lineq_q32_fn = &itsolv_rc::make_rc_linear_equations_q32;  // the same
+const auto make_diis_q32_fn = &itsolv_rc::make_rc_diis_q32;                // the same
 
 using Solver = it::IterativeSolverTemplate<Vec, Vec, SparseP>;
 using Davidson = it::LinearEigensystemDavidson<Vec, Vec, SparseP>;
@@ -411,6 +412,7 @@ int IterativeSolverHbmSetThrow(int enable) {
 }
 
 int IterativeSolverHbmSetContext(ssp_ctx* ctx) {
+  g_error.clear();  // (a call that cannot fail: it does not leave the error of a refused Initialize before it standing)
   g_user_ctx = ctx;
   return 0;
 }
@@ -525,9 +527,28 @@ void IterativeSolverNonLinearEquationsInitialize(size_t n, size_t* range_begin, 
                                                  const char* algorithm, const char* options) {
   guarded([&] {
     (void)fname;
-    refuse_q_options(options, "NonLinearEquations");
+    // extension: Q_STORAGE=f32 (one rank, "DIIS"): the history as f32 differences behind f64 anchors, which needs
+    // no refinement -- Q_REFINE stays refused
+    const auto q = q_options(options);
+    const std::string method = algorithm ? algorithm : "";
+    if (q.refine) throw std::invalid_argument("Q_REFINE: not available for NonLinearEquations");
+    if (q.f32 && !(method == "DIIS" || method.empty()))
+      throw std::invalid_argument("Q_STORAGE=f32: available for the NonLinearEquations DIIS only, not " + method);
+    if (q.f32 && !make_diis_q32_fn)
+      throw std::logic_error("Q_STORAGE=f32: SSP_ERR_UNSUPPORTED: not available for NonLinearEquations here: the loaded "
+                             "vector library has no mixed-precision ABI");
     Instance in;
     in.dev = make_device(fcomm);
+    if (q.f32 && in.dev->nranks() > 1)
+      throw std::invalid_argument("Q_STORAGE=f32: NonLinearEquations: not available on an instance with more than one rank");
+    if (q.f32) {  // the same construction over make_handlers_q32() (host_q32/rc_q32.cpp)
+      in.solver = make_diis_q32_fn(options ? options : "");
+      in.solver->set_convergence_threshold(thresh);
+      in.solver->set_verbosity(verbosity_of(verbosity));
+      setup(in, n, range_begin, range_end);
+      push(std::move(in));
+      return;
+    }
     auto handlers = molpro::linalg::hbm::make_handlers();
     auto solver = it::create_NonLinearEquations(algorithm ? algorithm : "", options ? options : "", handlers);
     solver->set_convergence_threshold(thresh);

@@ -156,5 +156,9 @@ std::unique_ptr<RcSolver> make_rc_davidson_q32(const std::string& options, size_
 std::unique_ptr<RcSolver> make_rc_linear_equations_q32(const std::string& options, std::vector<Vec>& rhs, bool hermitian,
                                                        double augmented_hessian, const it::RefineOptions& refine)
     __attribute__((weak));
+// NonLinearEquations "DIIS" over the same handlers with its history stored as f32 differences behind f64 anchors
+// (itsolv_hbm/diis_differences.h: NonLinearEquationsDIISDifferences<Vec, VecF32, SparseP>), options parsed as
+// create_NonLinearEquations parses them.  Weak: null without host_q32/.
+std::unique_ptr<RcSolver> make_rc_diis_q32(const std::string& options) __attribute__((weak));
 
 }  // namespace itsolv_rc

@@ -1,8 +1,9 @@
 // Q_STORAGE=f32 of the reverse-communication C API (include/iterative_solver_c.h): the instance's solver as
-// LinearEigensystemDavidson<Vec, VecF32, SparseP> or LinearEquationsDavidson<Vec, VecF32, SparseP> over
-// make_handlers_q32(), behind the Q-independent face of host/rc_solver.h.  It lives here, not in host/, for the reason host_q32/itsolv_q32.cpp does: the handlers
+// LinearEigensystemDavidson<Vec, VecF32, SparseP>, LinearEquationsDavidson<Vec, VecF32, SparseP> or
+// NonLinearEquationsDIISDifferences<Vec, VecF32, SparseP> over make_handlers_q32(), behind the Q-independent face of host/rc_solver.h.  It lives here, not in host/, for the reason host_q32/itsolv_q32.cpp does: the handlers
 // call the mixed-precision C ABI, which the CPU emulation that host/ is also linked against does not have.
 #include "../host/rc_solver.h"
+#include "itsolv_hbm/diis_differences.h"
 #include "itsolv_hbm/hbm_handlers_f32.h"
 #include "itsolv_hbm/solver_factory.h"
 
@@ -32,6 +33,14 @@ std::unique_ptr<RcSolver> make_rc_linear_equations_q32(const std::string& option
   s->add_equations(rhs);
   if (augmented_hessian > 0) s->set_augmented_hessian(augmented_hessian);
   if (refine.on) s->validate_refine();
+  return std::make_unique<RcSolverOf<VecF32>>(std::move(solver), std::move(handlers), sizeof(float));
+}
+
+std::unique_ptr<RcSolver> make_rc_diis_q32(const std::string& options) {
+  using molpro::linalg::hbm::VecF32;
+  auto handlers = molpro::linalg::hbm::make_handlers_q32();
+  auto solver = std::make_unique<it::NonLinearEquationsDIISDifferences<Vec, VecF32, SparseP>>(handlers);
+  solver->set_options(it::NonLinearEquationsDIISOptions{it::parse_options(options)});  // create_NonLinearEquations'
   return std::make_unique<RcSolverOf<VecF32>>(std::move(solver), std::move(handlers), sizeof(float));
 }
 

@@ -441,6 +441,23 @@ bool quantise_for_storage(H&, const RefR&) {
   return false;
 }
 
+// Hooks for a DIIS history stored as differences (diis_differences.h), where Q may be stored narrower than R.
+// `qr` is the Q x R handler, `rq` the R x Q handler.  Found by argument-dependent lookup.
+//  * fused_store_differences: appends out[j] = (Q)(vv[j] - aa[j]) as new Q vectors, the subtraction in R's
+//    precision and rounded once on narrowing, then aa[j] = vv[j], in one pass; returns false, touching nothing,
+//    when the handler has no such form (the caller then copies, subtracts, narrows and copies).
+//  * fused_anchor_combine: yy[j] = aa[j] - sum_i gammas[i] dd[j][i] for panels j that share the coefficients,
+//    the destinations written without being read, sources applied in order i = 0..; returns false, touching
+//    nothing, when the handler has no such form (the caller then copies the anchor and issues one gemm_outer).
+template <class H, class RefCR, class RefR, class Q>
+bool fused_store_differences(H&, const RefCR&, const RefR&, std::vector<Q>&) {
+  return false;
+}
+template <class H, class RefCR, class RefQ, class RefR>
+bool fused_anchor_combine(H&, const std::vector<double>&, const RefCR&, const std::vector<RefQ>&, const RefR&) {
+  return false;
+}
+
 // Hook for a fused sequential self-orthonormalisation of R (reference propose_rspace.h:450-465):
 // returns false when the handler has no fused form (the caller then runs the reference loop of
 // dot / scal / dot / axpy calls).  Found by argument-dependent lookup.

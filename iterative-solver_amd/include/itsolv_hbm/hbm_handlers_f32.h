@@ -534,4 +534,57 @@ inline bool fused_new_combinations_widened(array::ArrayHandler<VecF32, VecF32>&,
   return true;
 }
 
+// A DIIS history stored as f32 differences behind f64 anchors (diis_differences.h).
+// array::fused_store_differences hook: one ssp_q32_store_differences writes the new differences (allocated here,
+// never copied or zeroed) and refreshes the anchors -- 28 bytes per element and vector, bit for bit what the
+// copy, axpy(-1), narrowing copy and copy of the fallback store.  From fused_min_size(), as the other fused passes.
+inline bool fused_store_differences(array::ArrayHandler<VecF32, Vec>&, const itsolv::CVecRef<Vec>& vv,
+                                    const itsolv::VecRef<Vec>& aa, std::vector<VecF32>& out) {
+  const size_t m = vv.size();
+  if (m == 0 || aa.size() != m || vv.front().get().size() < fused_min_size()) return false;
+  const Vec& v0 = vv.front().get();
+  for (size_t j = 0; j < m; ++j)
+    if (!vv[j].get().compatible(v0) || !aa[j].get().compatible(v0))
+      throw array::util::ArrayHandlerError{"fused_store_differences: arrays have different distributions"};
+  std::vector<const double*> vp;
+  std::vector<double*> ap;
+  std::vector<float*> dp;
+  for (auto& v : vv) vp.push_back(v.get().data());  // (a pending scale is stored first)
+  for (auto& a : aa) ap.push_back(a.get().data_rw());  // (an anchor that still shares a caller's block gets its own)
+  const size_t first = out.size();
+  for (size_t j = 0; j < m; ++j) out.emplace_back(v0.device(), v0.size());
+  for (size_t j = 0; j < m; ++j) dp.push_back(out[first + j].data());
+  check(ssp_q32_store_differences(v0.ctx(), vp.data(), ap.data(), dp.data(), int(m), v0.local_size()),
+        "ssp_q32_store_differences");
+  return true;
+}
+
+// array::fused_anchor_combine hook: one ssp_q32_anchor_combine for the panels of a step (the parameters and the
+// residuals), write-only destinations -- bit for bit the anchor's copy and the gemm_outer of the fallback.  From
+// fused_min_size(), as the other fused passes.
+inline bool fused_anchor_combine(array::ArrayHandler<Vec, VecF32>&, const std::vector<double>& gammas,
+                                 const itsolv::CVecRef<Vec>& aa, const std::vector<itsolv::CVecRef<VecF32>>& dd,
+                                 const itsolv::VecRef<Vec>& yy) {
+  const size_t m = yy.size(), k = gammas.size();
+  if (m == 0 || aa.size() != m || dd.size() != m || yy.front().get().size() < fused_min_size()) return false;
+  const Vec& y0 = yy.front().get();
+  std::vector<const double*> ap;
+  std::vector<const float*> dp;
+  for (size_t j = 0; j < m; ++j) {
+    if (dd[j].size() != k || !aa[j].get().compatible(y0) || !yy[j].get().compatible(y0))
+      throw array::util::ArrayHandlerError{"fused_anchor_combine: arrays have different distributions"};
+    ap.push_back(aa[j].get().data());
+    for (auto& d : dd[j]) {
+      if (!d.get().compatible(y0))
+        throw array::util::ArrayHandlerError{"fused_anchor_combine: arrays have different distributions"};
+      dp.push_back(d.get().data());
+    }
+  }
+  // write-only destinations: one that still shares an anchor's block is given a fresh block, nothing is copied
+  auto yp = detail::wo_ptrs(yy);
+  check(ssp_q32_anchor_combine(y0.ctx(), gammas.data(), ap.data(), dp.data(), int(k), yp.data(), int(m), y0.local_size()),
+        "ssp_q32_anchor_combine");
+  return true;
+}
+
 }  // namespace molpro::linalg::hbm

@@ -329,12 +329,14 @@ void run_optimize(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Proble
   if (emit) emit(xs);
 }
 
-// Runs NonLinearEquationsDIIS::solve from x0 (set by init) and fills `out`.
-template <class R, class Q, class P>
-void run_diis(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Problem<R, P>& problem,
-              const std::function<R()>& make_vec, const std::function<void(R&)>& init,
-              const itsolv_options& o, itsolv_result& out, const std::function<void(const R&)>& emit) {
-  NonLinearEquationsDIIS<R, Q, P> solver(handlers);
+// Runs Solver::solve from x0 (set by init) and fills `out`.  Solver: NonLinearEquationsDIIS<R, Q, P> or a solver
+// derived from it (diis_differences.h); after_solve (optional) sees the solver before its solution is extracted.
+template <class Solver, class R, class Q, class P>
+void run_diis_with(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Problem<R, P>& problem,
+                   const std::function<R()>& make_vec, const std::function<void(R&)>& init, const itsolv_options& o,
+                   itsolv_result& out, const std::function<void(const R&)>& emit,
+                   const std::function<void(const Solver&)>& after_solve = {}) {
+  Solver solver(handlers);
   NonLinearEquationsDIISOptions opt;
   apply_options(o, opt);
   opt.n_roots = 1;
@@ -347,6 +349,7 @@ void run_diis(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Problem<R,
   const SolveClock clock;
   out.converged = solver.solve(x, g, problem);
   clock.finish(solver, out);
+  if (after_solve) after_solve(solver);
   out.nroots = 1;
   out.errors[0] = solver.errors().empty() ? 0.0 : solver.errors().front();
   out.eigenvalues[0] = 0;
@@ -357,6 +360,14 @@ void run_diis(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Problem<R,
   problem.residual(xs, gs);
   out.residual_norms[0] = std::sqrt(std::abs(handlers->rr().dot(gs, gs)));
   if (emit) emit(xs);
+}
+
+// Runs NonLinearEquationsDIIS::solve from x0 (set by init) and fills `out`.
+template <class R, class Q, class P>
+void run_diis(std::shared_ptr<ArrayHandlers<R, Q, P>> handlers, const Problem<R, P>& problem,
+              const std::function<R()>& make_vec, const std::function<void(R&)>& init,
+              const itsolv_options& o, itsolv_result& out, const std::function<void(const R&)>& emit) {
+  run_diis_with<NonLinearEquationsDIIS<R, Q, P>, R, Q, P>(std::move(handlers), problem, make_vec, init, o, out, emit);
 }
 
 inline void default_options(itsolv_options* o) {

@@ -357,8 +357,10 @@ class IterativeSolverTemplate {
     return add_vector(wrap_arg(parameters), wrap_arg(actions));
   }
 
-  size_t add_p(const CVecRef<P>& pparams, const std::vector<double>& pp_action_matrix, const VecRef<R>& parameters,
-               const VecRef<R>& actions, fapply_on_p_type apply_p) {
+  // (add_p, solution, solution_params and dimensions are virtual for a solver that keeps its history outside the
+  // XSpace: diis_differences.h)
+  virtual size_t add_p(const CVecRef<P>& pparams, const std::vector<double>& pp_action_matrix, const VecRef<R>& parameters,
+                       const VecRef<R>& actions, fapply_on_p_type apply_p) {
     if (!pparams.empty() && pparams.size() < n_roots())
       throw std::runtime_error("P space must be empty or at least as large as number of roots sought");
     if (apply_p) m_apply_p = std::move(apply_p);
@@ -368,7 +370,7 @@ class IterativeSolverTemplate {
     return ws;
   }
 
-  void solution(const std::vector<int>& roots, const VecRef<R>& parameters, const VecRef<R>& residual) {
+  virtual void solution(const std::vector<int>& roots, const VecRef<R>& parameters, const VecRef<R>& residual) {
     check_roots(roots, parameters.size());
     const auto& d = m_xspace->dimensions();
     detail::construct_solution(parameters, roots, m_subspace_solver->solutions(), m_xspace->cparamsp(),
@@ -386,7 +388,7 @@ class IterativeSolverTemplate {
   }
   void solution(R& parameters, R& residual) { solution(std::vector<int>(1, 0), wrap_arg(parameters), wrap_arg(residual)); }
 
-  void solution_params(const std::vector<int>& roots, const VecRef<R>& parameters) {
+  virtual void solution_params(const std::vector<int>& roots, const VecRef<R>& parameters) {
     check_roots(roots, parameters.size());
     const auto& d = m_xspace->dimensions();
     detail::construct_solution(parameters, roots, m_subspace_solver->solutions(), m_xspace->cparamsp(),
@@ -410,7 +412,7 @@ class IterativeSolverTemplate {
   }
   const std::vector<double>& errors() const { return m_errors; }
   const Statistics& statistics() const { return *m_stats; }
-  const subspace::Dimensions& dimensions() const { return m_xspace->dimensions(); }
+  virtual const subspace::Dimensions& dimensions() const { return m_xspace->dimensions(); }
   //! Latest function value of an Optimize solver, NaN otherwise (reference IterativeSolverTemplate.h:312-315)
   double value() const {
     const auto it = m_xspace->data.find(EqnData::value);

@@ -30,12 +30,16 @@ EXPORTS = [
     "itsolv_linear_equations_synth",
     "itsolv_linear_equations_dense_q32", "itsolv_linear_equations_synth_q32",
     "itsolv_linear_equations_dense_q32_refined", "itsolv_linear_equations_synth_q32_refined",
+    # DIIS with its history stored as f32 differences behind f64 anchors, and what the last such solve held
+    "itsolv_diis_synth_q32", "itsolv_diis_dense_q32", "itsolv_q32_diis_stats",
 ]
 # Linear equations over the f32 Q space: absent from the CPU emulation of the library, as the sets below; a set
 # of their own (those stay what they were).
 OPTIONAL_LINEQ = frozenset(n for n in EXPORTS if n.startswith("itsolv_linear_equations_") and "_q32" in n)
 # Absent from the CPU emulation of the library (loaded through this binding by patching LIB_PATH).
-OPTIONAL = frozenset(n for n in EXPORTS if n.endswith("_q32")) - OPTIONAL_LINEQ
+# DIIS over f32 differences: absent from the emulation in the same way; again a set of its own.
+OPTIONAL_DIIS = frozenset(n for n in EXPORTS if n.startswith("itsolv_diis_") and n.endswith("_q32")) | {"itsolv_q32_diis_stats"}
+OPTIONAL = frozenset(n for n in EXPORTS if n.endswith("_q32")) - OPTIONAL_LINEQ - OPTIONAL_DIIS
 # The refined mode's entry points, optional in the same way; a set of their own: OPTIONAL stays the plain f32 Q space.
 OPTIONAL_REFINED = (frozenset(n for n in EXPORTS if n.endswith("_q32_refined") or n == "itsolv_q32_refine_stats")
                     - OPTIONAL_LINEQ)
@@ -184,8 +188,11 @@ def load_library():
             "itsolv_linear_equations_synth_q32": (I, [P, Z, C.POINTER(Synth), I, U, PO, PR, PD]),
             "itsolv_linear_equations_dense_q32_refined": (I, [P, PD, Z, PD, I, PO, PF, PR, PD]),
             "itsolv_linear_equations_synth_q32_refined": (I, [P, Z, C.POINTER(Synth), I, U, PO, PF, PR, PD]),
+            "itsolv_diis_synth_q32": (I, [P, Z, C.POINTER(Synth), PO, PR, PD]),
+            "itsolv_diis_dense_q32": (I, [P, PD, Z, PO, PR, PD]),
+            "itsolv_q32_diis_stats": (I, [PI, PI, C.POINTER(C.c_size_t)]),
         }
-        optional = OPTIONAL | OPTIONAL_REFINED | OPTIONAL_DSPACE | OPTIONAL_LINEQ
+        optional = OPTIONAL | OPTIONAL_REFINED | OPTIONAL_DSPACE | OPTIONAL_LINEQ | OPTIONAL_DIIS
         for name, (res, args) in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -285,25 +292,39 @@ def davidson_dense(ctx: sh.Context, h: np.ndarray, q32: bool = False, refine: bo
     return r
 
 
+def _diis_stats() -> dict:
+    p, d, b = C.c_int(), C.c_int(), C.c_size_t()
+    load_library().itsolv_q32_diis_stats(C.byref(p), C.byref(d), C.byref(b))
+    return {"points": p.value, "pairs": d.value, "history_bytes": b.value}
+
+
 def diis_synthetic(ctx: sh.Context, n: int, rho: float, rank: int, seed: int, n_local: int | None = None,
                    solutions: bool = True, *, diag_kind: int = DIAG_LINEAR, alpha: float = 0.0,
-                       target: float = 1.0, **opts):
+                       target: float = 1.0, q32: bool = False, **opts):
+    """q32: the history is held as f32 differences between successive iterates behind two f64 anchors
+    (include/itsolv_hbm.h itsolv_diis_synth_q32): about half the HBM of the f64 history, f64 thresholds, the
+    iterations of the f64 solve; the result then has "diis_q32" (points, pairs of differences, history bytes)."""
     o = make_options(**opts)
     nl = n if n_local is None else n_local
     spec = Synth(rho, rank, seed, diag_kind, alpha, target)
-    r, x = _call(load_library().itsolv_diis_synth, (ctx.handle, n, C.byref(spec), C.byref(o)),
+    r, x = _call(_entry("itsolv_diis_synth", q32), (ctx.handle, n, C.byref(spec), C.byref(o)),
                  nl if solutions else 0)
+    if q32:
+        r["diis_q32"] = _diis_stats()
     if solutions:
         r["x"] = x[:nl]
     return r
 
 
-def diis_dense(ctx: sh.Context, h: np.ndarray, **opts):
+def diis_dense(ctx: sh.Context, h: np.ndarray, q32: bool = False, **opts):
+    """q32: as diis_synthetic's."""
     h = np.ascontiguousarray(h, dtype=np.float64)
     n = h.shape[0]
     o = make_options(**opts)
-    r, x = _call(load_library().itsolv_diis_dense, (ctx.handle, h.ctypes.data_as(C.POINTER(C.c_double)), n,
-                                                    C.byref(o)), n)
+    r, x = _call(_entry("itsolv_diis_dense", q32), (ctx.handle, h.ctypes.data_as(C.POINTER(C.c_double)), n,
+                                                   C.byref(o)), n)
+    if q32:
+        r["diis_q32"] = _diis_stats()
     r["x"] = x[:n]
     return r
 

@@ -64,6 +64,8 @@ EXPORTS = [
     "ssp_q32_combine_widen",
     # residuals against right-hand sides and their norms in one pass (linear equations over an f32 Q space)
     "ssp_mx_rhs_residual_norms",
+    # a DIIS history stored as f32 differences behind f64 anchors
+    "ssp_q32_store_differences", "ssp_q32_anchor_combine",
 ]
 
 # The mixed-precision entry points are optional in a loaded library: the CPU emulation of the f64 C ABI
@@ -79,7 +81,9 @@ OPTIONAL = (frozenset(n for n in EXPORTS if n.endswith("_f32") or n.startswith("
 # raises SspError(SSP_ERR_UNSUPPORTED)); they are a set of their own: OPTIONAL stays the storage layer.
 # The combine-and-widen pass of the refined mode's D space, optional in the same way; again a set of its own.
 OPTIONAL_DSPACE = frozenset({"ssp_q32_combine_widen"})
-OPTIONAL_Q32 = frozenset(n for n in EXPORTS if n.startswith("ssp_q32_")) - OPTIONAL_DSPACE
+# The two passes of the DIIS history stored as differences, optional in the same way; again a set of its own.
+OPTIONAL_DIIS = frozenset({"ssp_q32_store_differences", "ssp_q32_anchor_combine"})
+OPTIONAL_Q32 = frozenset(n for n in EXPORTS if n.startswith("ssp_q32_")) - OPTIONAL_DSPACE - OPTIONAL_DIIS
 # The row-block entry points (a caller's device block <-> library vectors), optional in the same way and a
 # set of their own: the three sets above stay what they were.
 OPTIONAL_ROWS = frozenset({"ssp_rows_import", "ssp_rows_export"})
@@ -216,11 +220,14 @@ def _declare(lib):
         "ssp_q32_construct_solution": (I, [P, PD, PZ, PZ, PD, I, PD, P, I, P, I, Z, Z]),
         "ssp_q32_block_update": (I, [P, PD, PZ, PZ, PD, I, PD, P, I, P, PD, I, Z, Z]),
         "ssp_q32_combine_widen": (I, [P, PD, P, I, P, P, I, Z]),
+        "ssp_q32_store_differences": (I, [P, P, P, P, I, Z]),
+        "ssp_q32_anchor_combine": (I, [P, PD, P, P, I, P, I, Z]),
         "ssp_rows_import": (I, [P, P, Z, P, I, Z]),
         "ssp_rows_export": (I, [P, P, PD, I, P, Z, Z]),
         "ssp_rows_export_quantised": (I, [P, P, PD, I, I, P, Z, Z]),
     }
-    optional = OPTIONAL | OPTIONAL_Q32 | OPTIONAL_REFINED | OPTIONAL_ROWS | OPTIONAL_ROWS_Q | OPTIONAL_DSPACE | OPTIONAL_LINEQ
+    optional = (OPTIONAL | OPTIONAL_Q32 | OPTIONAL_REFINED | OPTIONAL_ROWS | OPTIONAL_ROWS_Q | OPTIONAL_DSPACE | OPTIONAL_LINEQ
+                | OPTIONAL_DIIS)
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -988,6 +995,33 @@ class Context:
         al = np.ascontiguousarray(alphas, dtype=np.float64).reshape(len(xx), len(yy))
         n = yy[0].n if yy else 0
         _check(f(self.handle, _dptr(al), _ptrs(xx), len(xx), _ptrs(yy), _ptrs(ww), len(yy), n))
+
+    def q32_store_differences(self, vv, aa, dd=None):
+        """dd[j] = float32(vv[j] - aa[j]), then aa[j] = vv[j], in one pass (ssp_q32_store_differences): float64 new
+        points vv and anchors aa, float32 differences dd; dd None: the anchors only."""
+        f = self._mx("ssp_q32_store_differences")
+        if any(_code(v) != SSP_F64 for v in list(vv) + list(aa)) or any(_code(v) != SSP_F32 for v in dd or ()):
+            raise TypeError("q32_store_differences: float64 points and anchors, float32 differences")
+        if len(aa) != len(vv) or (dd is not None and len(dd) != len(vv)):
+            raise ValueError("q32_store_differences: one anchor and one difference per point")
+        n = vv[0].n if vv else 0
+        _check(f(self.handle, _ptrs(vv), _ptrs(aa), None if dd is None else _ptrs(dd), len(vv), n))
+
+    def q32_anchor_combine(self, gammas, aa, dd, yy):
+        """yy[j] = aa[j] - sum_i gammas[i] float64(dd[j][i]) in one write-only pass (ssp_q32_anchor_combine): float64
+        anchors aa and destinations yy, dd[j] the float32 differences of panel j (the same number for every j)."""
+        f = self._mx("ssp_q32_anchor_combine")
+        m = len(yy)
+        if len(aa) != m or len(dd) != m:
+            raise ValueError("q32_anchor_combine: one anchor and one list of differences per destination")
+        g = np.ascontiguousarray(gammas, dtype=np.float64).reshape(-1)
+        flat = [d for panel in dd for d in panel]
+        if any(len(panel) != g.size for panel in dd):
+            raise ValueError("q32_anchor_combine: one coefficient per difference of every panel")
+        if any(_code(v) != SSP_F64 for v in list(aa) + list(yy)) or any(_code(v) != SSP_F32 for v in flat):
+            raise TypeError("q32_anchor_combine: float64 anchors and destinations, float32 differences")
+        n = yy[0].n if m else 0
+        _check(f(self.handle, _dptr(g) if g.size else None, _ptrs(aa), _ptrs(flat), g.size, _ptrs(yy), m, n))
 
     @staticmethod
     def _f32_sources(xx, what):
